@@ -19,8 +19,12 @@ flat-label kernels overlap the next partitions' work.  Every step still does all
 
 Prints ONE JSON line (rank 0).  value = points/s over all ranks, end to end from parsed points
 in pinned host memory (every step uploads its points inside the timed region) to the merged
-list and labels back in host memory; hbm_resident_points_per_s = the same pipeline from points
-already in HBM; device_resident_points_per_s = MST + merge only (HBM to HBM, no labels).
+list and labels back in host memory.  A plain run sets up, warms up, times --steps steps and
+prints that headline (ms_per_step = one timed step).  --full adds the passes that take runs of
+their own: hbm_resident_points_per_s = the same pipeline from points
+already in HBM; device_resident_points_per_s = MST + merge only (HBM to HBM, no labels); the
+one-partition latency, the per-kernel times and roofline, the spanning-tree check and the CPU
+baseline.  --dump-outputs DIR writes the last timed step's merged edge list and labels.
 """
 from __future__ import annotations
 
@@ -247,6 +251,8 @@ def run_c4(args):
     t0 = time.perf_counter()
     run(args.steps, resident=False)
     dt = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"core": core_h.numpy()})
     # X already resident in HBM (beside the value, never as it); its HIP events time the kernels
     ctx.set_timing(True)
     for name in ("knn_mfma", "knn_mfma_final", "knn_mfma_order"):
@@ -546,6 +552,9 @@ def run_partitioned(args, workload):
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
+    if args.dump_outputs and rank == 0:  # before the diagnostic jobs below overwrite `out`
+        dump_outputs(args.dump_outputs, {"merged_vertex_a": out["edges"][0].numpy(), "merged_vertex_b": out["edges"][1].numpy(),
+                                         "merged_weight": out["edges"][2].numpy(), "labels": out["labels"].numpy()})
     r = out["r"]
     kt = kernel_totals()
     coop_steps = stat_total("prim_coop_steps") - steps0
@@ -642,6 +651,25 @@ def emit(line):
     print(json.dumps(line), flush=True)
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array of the last timed step's result as dirname/<name>.npy in
+    float64 (ids and labels are exact there).  Above DUMP_MAX_BYTES in all, every array keeps
+    the same fraction of its entries: ascending indices drawn from a generator seeded by the
+    array's length, so two runs keep the same entries and the columns of one edge list stay
+    aligned."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.asarray(v).reshape(-1) for k, v in arrays.items()}
+    total = 8 * sum(v.shape[0] for v in arrays.values())
+    for name, v in arrays.items():
+        if total > DUMP_MAX_BYTES:
+            m = int(v.shape[0] * (DUMP_MAX_BYTES / total))
+            v = v[np.sort(np.random.default_rng([7, v.shape[0]]).choice(v.shape[0], size=m, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), v.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -649,6 +677,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=None, help="default 5 (c2), 2 (c4), 0 (c3/c5)")
     ap.add_argument("--n", type=int, default=N_POINTS)
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="c2: after the timed steps also run the HBM-resident, latency and device-resident passes, "
+                         "the output checks, the executed-work pass, the roofline and the CPU baseline (off: set "
+                         "up, warm up, time --steps steps, print the headline line).  c3/c4/c5 are separate "
+                         "workloads asked for by name and always print their whole line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step handed back (merged edge list and labels; c4: core "
+                         "distances) as DIR/<name>.npy")
     ap.add_argument("--workload", choices=["c2", "c3", "c4", "c5"], default="c2",
                     help="c2 (default): the per-GPU C2 pipeline (weak scaling); c3/c5: the whole "
                          "partitioned job over the sharded driver (strong scaling)")
@@ -882,6 +918,10 @@ def main():
             self.st[self.k % len(self.st)].submit(own, merged)
             self.k += 1
 
+        def last_bufs(self):
+            """the host buffers of the stage that took the last submitted step"""
+            return self.st[(self.k - 1) % len(self.st)].bufs
+
         def drain(self):
             for x in self.st:
                 x.drain()
@@ -950,7 +990,8 @@ def main():
         return float(t.item())
 
     pipe_run(args.warmup)
-    pipe_run(1, resident=True)  # the HBM-resident path warm too
+    if args.full:
+        pipe_run(1, resident=True)  # the HBM-resident path warm too
     barrier()
     # the value: every step's points uploaded from pinned host memory inside the timed region
     # (from parsed points resident in host memory)
@@ -958,6 +999,63 @@ def main():
     pipe_run(args.steps)
     barrier()
     dt = max_over_ranks(time.perf_counter() - t0)
+    tsteps = args.steps
+    total_points = world * n
+    value = total_points * tsteps / dt
+    evals = world * (n * n + n * (n - 1) / 2)  # kNN n^2 + MST n(n-1)/2 (SURVEY §8(d))
+    # the last timed step's host outputs (its label stage's pinned buffers): cheap sanity
+    # checks on what the headline timed, and the arrays --dump-outputs writes
+    last = stage.last_bufs()
+    lab_last = last[3].numpy()
+    assert lab_last.min() >= 0 and lab_last.max() == n_clusters[0]
+    if rank == 0:
+        w_last = last[2].numpy()
+        assert w_last.shape[0] == world * ne_local and np.all(w_last[:-1] >= w_last[1:]), "merged list not descending"
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"merged_vertex_a": last[0].numpy(), "merged_vertex_b": last[1].numpy(),
+                                             "merged_weight": w_last, "labels": lab_last})
+    line = {
+        "metric": "points/sec end-to-end + mutual-reach distance evals/sec at 1/2/4/8 GPUs",
+        "value": value,
+        "unit": "points/s",
+        "n_gpus": world,
+        "steps": tsteps,
+        "warmup": args.warmup,
+        "ms_per_step": dt * 1e3 / tsteps,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (seeded Gaussian blobs, 20 centers ~U[-100,100]^3, sigma 1, seed 1+rank)",
+        "config": {"workload": "config 2: blobs 1M x 3 exact HDBSCAN* (no sampling), minPts 4, minClSize 4",
+                   "points_per_gpu": n, "d": D, "min_pts": MIN_PTS, "min_cl_size": MIN_CL_SIZE,
+                   "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "0") or 0),
+                   "core": "EXCL_SELF", "timed": "X in pinned host memory -> H2D (each stage-1 worker uploads "
+                   "its step's points on its own stream) -> K1t cores -> K2b MST + self edges, in the merge "
+                   "order (HDB_EDGES_MERGED: tree edges sorted descending, self edges by core, one merge-path pass) "
+                   "-> N>1: gather to rank 0, merge of the presorted runs -> "
+                   "K6 flat labels of the partition (D2H of the merged list overlapping it on a copy "
+                   "stream) -> D2H of the labels; pipelined: step i's labels + D2H (own thread, stream and "
+                   "library context) overlap step i+1's MST + merge; the timer stops after the last step's "
+                   "labels are on the host",
+                   "stage1_partitions_in_flight": M, "label_stages": L,
+                   "parallelism": f"partition-sharded x{world}"},
+        "n_clusters": n_clusters[0],
+        "mrd_evals_per_s": evals * tsteps / dt,
+        "mrd_evals_per_s_kind": "algorithmic-equivalent: n^2 (k-NN) + n(n-1)/2 (MST) per partition (SURVEY.md "
+                                "8(d)) over the step time; the exact pruned kernels execute ~1/1000 of it "
+                                "(--full: executed_pair_evals_per_s)",
+        "full": bool(args.full),
+    }
+    if not args.full:  # the headline alone: nothing else is measured or checked
+        stage.close()
+        if workers is not None:
+            workers.close()
+        if rank == 0:
+            emit(line)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # the same pipeline from points already resident in HBM (reported beside the value, never as it)
     barrier()
     t0 = time.perf_counter()
@@ -996,7 +1094,6 @@ def main():
     dt_dev = max_over_ranks(time.perf_counter() - t0)
     kt_seq = {k: ctx.kernel_time(k) for k in keys}
     ctx.set_timing(False)
-    tsteps = args.steps
 
     # checks on the last end-to-end step's host outputs
     if rank == 0:
@@ -1028,8 +1125,6 @@ def main():
         rounds.append((visits, waves))
     ctx.set_option("count_evals", 0)
 
-    total_points = world * n
-    value = total_points * tsteps / dt
     # per-partition kernel times, each kernel alone (one partition at a time: the device-resident
     # pass for stage 1, the latency pass for the labels)
     ms = {k: v[0] / tsteps for k, v in kt_seq.items()} | {"flat_labels": kt_lab[0] / tsteps}
@@ -1048,34 +1143,7 @@ def main():
     traffic = None
     traffic = _pmc_bytes(PMC_C2, "boruvka_bvh_kernel")
     fp64_tflops = 3 * D * (bor_evals / max(scan_n / tsteps, 1)) / avg_scan_s / 1e12 if avg_scan_s > 0 else 0.0
-    evals = world * (n * n + n * (n - 1) / 2)  # kNN n^2 + MST n(n-1)/2 (SURVEY §8(d))
-    line = {
-        "metric": "points/sec end-to-end + mutual-reach distance evals/sec at 1/2/4/8 GPUs",
-        "value": value,
-        "unit": "points/s",
-        "n_gpus": world,
-        "steps": tsteps,
-        "warmup": args.warmup,
-        "ms_per_step": dt * 1e3 / tsteps,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic (seeded Gaussian blobs, 20 centers ~U[-100,100]^3, sigma 1, seed 1+rank)",
-        "config": {"workload": "config 2: blobs 1M x 3 exact HDBSCAN* (no sampling), minPts 4, minClSize 4",
-                   "points_per_gpu": n, "d": D, "min_pts": MIN_PTS, "min_cl_size": MIN_CL_SIZE,
-                   "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "0") or 0),
-                   "core": "EXCL_SELF", "timed": "X in pinned host memory -> H2D (each stage-1 worker uploads "
-                   "its step's points on its own stream) -> K1t cores -> K2b MST + self edges, in the merge "
-                   "order (HDB_EDGES_MERGED: tree edges sorted descending, self edges by core, one merge-path pass) "
-                   "-> N>1: gather to rank 0, merge of the presorted runs -> "
-                   "K6 flat labels of the partition (D2H of the merged list overlapping it on a copy "
-                   "stream) -> D2H of the labels; pipelined: step i's labels + D2H (own thread, stream and "
-                   "library context) overlap step i+1's MST + merge; the timer stops after the last step's "
-                   "labels are on the host",
-                   "stage1_partitions_in_flight": M, "label_stages": L,
-                   "parallelism": f"partition-sharded x{world}"},
-        "n_clusters": n_clusters[0],
+    line.update({
         "hbm_resident_points_per_s": total_points * tsteps / dt_hbm,
         "hbm_resident_ms_per_step": dt_hbm * 1e3 / tsteps,
         "hbm_resident_kind": "the same pipeline from points already resident in HBM (no H2D; not the value)",
@@ -1083,10 +1151,6 @@ def main():
         "latency_kind": "the same steps without the pipeline: each step's stages back to back",
         "device_resident_points_per_s": total_points * tsteps / dt_dev,
         "device_resident_ms_per_step": dt_dev * 1e3 / tsteps,
-        "mrd_evals_per_s": evals * tsteps / dt,
-        "mrd_evals_per_s_kind": "algorithmic-equivalent: n^2 (k-NN) + n(n-1)/2 (MST) per partition (SURVEY.md "
-                                "8(d)) over the step time; the exact pruned kernels execute ~1/1000 of it "
-                                "(executed_pair_evals_per_s)",
         "executed_pair_evals_per_s": world * (knn_evals + bor_evals) * tsteps / dt,
         "kernels_ms_per_partition": ms,
         "kernels_kind": "HIP events on the launch stream, one partition at a time (stage 1: the device-resident "
@@ -1108,7 +1172,7 @@ def main():
                               "work": "executed pair evals x 3d flops"},
                      "hbm": {"achieved_gbs": (traffic or 0) / avg_scan_s / 1e9 if avg_scan_s > 0 else 0.0,
                              "peak": HBM_PEAK_GBS}},
-    }
+    })
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(X_host)
     if rank == 0:

@@ -51,7 +51,17 @@ def blobs(n, d, centers, seed, spread=100.0, sigma=1.0):
 
 
 def golden(name):
-    return np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
+    """tests/golden/<name>.npz; a fixture too large for one committed file (1 MiB) continues in
+    <name>_part2.npz, ... (other arrays of the same fixture), merged here into one mapping"""
+    z = np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
+    parts = sorted(f for f in os.listdir(GOLDEN) if f.startswith(name + "_part") and f.endswith(".npz"))
+    if not parts:
+        return z
+    out = {k: z[k] for k in z.files}
+    for f in parts:
+        p = np.load(os.path.join(GOLDEN, f), allow_pickle=False)
+        out.update({k: p[k] for k in p.files})
+    return out
 
 
 def driver_levels(got):

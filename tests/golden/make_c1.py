@@ -1,4 +1,4 @@
-"""Generates tests/golden/c1_skin_full.npz: the CPU oracle's MR-HDBSCAN* (oracle/mr_driver.py,
+"""Generates tests/golden/c1_skin_full.npz (+ c1_skin_full_part2.npz): the CPU oracle's MR-HDBSCAN* (oracle/mr_driver.py,
 the line restatement of Main.java:103-347 with the deviations D1-D10) on ALL 245,057 rows of
 the reference's Skin_NonSkin.txt with the reference's hard-coded my_args (Main.java:71:
 minPts=4, minClSize=4, processing_units=50, k=0.2) and the D2 sample seed 20210101.
@@ -51,8 +51,13 @@ def main(out=os.path.join(HERE, "c1_skin_full.npz")):
         for k, code in sorted(L.get("model_errors", {}).items()):
             errs.append((L["iteration"], k, code))
     cat = lambda a, t: np.concatenate(a).astype(t) if a else np.zeros(0, t)
+    # two files, each under the 1 MiB limit for a committed file: vb alone in _part2
+    # (conftest.golden merges them)
+    part2 = out[:-len(".npz")] + "_part2.npz"
+    np.savez_compressed(part2, vb=vb)
+    print("wrote", part2, os.path.getsize(part2), "bytes")
     np.savez_compressed(
-        out, va=va, vb=vb, w=w, leaf_of=r["leaf_of"], labels=r["labels"], n_clusters=r["n_clusters"],
+        out, va=va, w=w, leaf_of=r["leaf_of"], labels=r["labels"], n_clusters=r["n_clusters"],
         iterations=r["iterations"], levels=np.asarray(lv, np.int64).reshape(-1, 4),
         label_keys=np.asarray(lab_keys, np.int64).reshape(-1, 2), label_off=np.asarray(lab_off, np.int64),
         label_vals=cat(lab_vals, np.int32), newkey_keys=np.asarray(nk_keys, np.int64).reshape(-1, 2),

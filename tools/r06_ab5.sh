@@ -5,7 +5,7 @@ set -uo pipefail
 OUT=${1:?outdir}; V=${2:?variant}; mkdir -p "$OUT"; export TMPDIR=/tmp
 for r in 1 2 3 4 5; do for v in default "$V"; do
   if [ "$v" = default ]; then unset HDBMI_LIB; else export HDBMI_LIB=$PWD/ab/$v/libhdbmi.so; fi
-  echo -n "$v "; timeout -k 10 200 python -u bench.py --no-cpu-baseline 2>>"$OUT/stderr.log" | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['ms_per_step'],3), round(d['hbm_resident_ms_per_step'],3), round(d['latency_ms_per_step'],3), round(d['kernels_ms_per_partition']['knn_tree'],3))"
+  echo -n "$v "; timeout -k 10 200 python -u bench.py --full --no-cpu-baseline 2>>"$OUT/stderr.log" | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['ms_per_step'],3), round(d['hbm_resident_ms_per_step'],3), round(d['latency_ms_per_step'],3), round(d['kernels_ms_per_partition']['knn_tree'],3))"
 done; done > "$OUT/ab.log" 2>&1
 python3 - "$OUT/ab.log" <<'PY'
 import sys, collections, statistics

@@ -11,7 +11,7 @@ for r in 1 2 3; do for x in 0 4 8 16; do
 done; done > "$OUT/part.log" 2>&1
 cat "$OUT/part.log"
 for r in 1 2 3; do for x in 0 4 8 16; do
-  echo -n "m=$x "; HDB_K1T_XCD=$x timeout -k 10 200 python -u bench.py --no-cpu-baseline 2>>"$OUT/stderr.log" | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['ms_per_step'],3), round(d['hbm_resident_ms_per_step'],3), round(d['latency_ms_per_step'],3))"
+  echo -n "m=$x "; HDB_K1T_XCD=$x timeout -k 10 200 python -u bench.py --full --no-cpu-baseline 2>>"$OUT/stderr.log" | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['ms_per_step'],3), round(d['hbm_resident_ms_per_step'],3), round(d['latency_ms_per_step'],3))"
 done; done > "$OUT/bench.log" 2>&1
 cat "$OUT/bench.log"
 for x in 0 4 8 16; do
