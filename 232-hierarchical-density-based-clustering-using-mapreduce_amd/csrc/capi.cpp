@@ -380,8 +380,9 @@ int hdb_quicksort_edges(int32_t *va, int32_t *vb, double *w, int64_t ne) {
     return rc;
 }
 
-// core_in (nullable, host, b values): the bubble core distances already computed by
-// hdb_bubble_core_distances on the same (rep, nB, eB, nnB) -- the model then starts at the Prim
+// core_in (nullable, host or device, b values): the bubble core distances already computed by
+// hdb_bubble_core_distances on the same (rep, nB, eB, nnB) -- the model then starts at the Prim.
+// The outputs are written by the host algorithm: host memory only (a device pointer is EINVAL)
 static int local_model_impl(hdb_ctx *ctx, const double *rep, const double *info, int64_t b, int32_t d,
                             int32_t min_pts, int32_t min_cl_size, int32_t metric, const double *core_in,
                             int32_t *labels, int32_t *mst_va, int32_t *mst_vb, double *mst_w, int32_t *ic_va,
@@ -390,6 +391,9 @@ static int local_model_impl(hdb_ctx *ctx, const double *rep, const double *info,
         check_metric(metric);
         if (b < 1 || d <= 0 || !rep || !info || !labels || min_pts < 1) HDB_THROW(HDB_EINVAL, "bad arguments");
         if (min_pts > 32) HDB_THROW(HDB_EINVAL, "minPts too large (max 32)");
+        for (const void *o : {(const void *)labels, (const void *)mst_va, (const void *)mst_vb, (const void *)mst_w,
+                              (const void *)ic_va, (const void *)ic_vb, (const void *)ic_w, (const void *)n_ic})
+            if (is_device_ptr(o)) HDB_THROW(HDB_EINVAL, "local model: outputs must be host memory (device pointer given)");
         std::vector<double> rep_h = to_host(ctx, rep, (size_t)(b * d));
         std::vector<double> info_h = to_host(ctx, info, (size_t)(b * 3));
         std::vector<double> eB(b), nnB(b);
@@ -407,7 +411,7 @@ static int local_model_impl(hdb_ctx *ctx, const double *rep, const double *info,
         auto t0 = clk::now();
         std::vector<double> core;
         if (core_in)
-            core.assign(core_in, core_in + b);
+            core = to_host(ctx, core_in, (size_t)b);
         else
             bubble_core_impl(ctx, rep_h.data(), nB.data(), eB.data(), nnB.data(), b, d, min_pts, metric, core);
         auto t1 = clk::now();
@@ -483,8 +487,7 @@ int hdb_merge_sorted_runs(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, co
                           int32_t nruns, int32_t *oa, int32_t *ob, double *ow) {
     return guarded(ctx, [&] {
         if (nruns < 0 || (nruns > 0 && !run_off)) HDB_THROW(HDB_EINVAL, "bad arguments");
-        std::vector<int64_t> off(run_off, run_off + nruns + 1);
-        if (nruns == 0) off.assign(1, 0);
+        std::vector<int64_t> off = nruns ? to_host(ctx, run_off, (size_t)nruns + 1) : std::vector<int64_t>(1, 0);
         for (int r = 0; r < nruns; r++)
             if (off[r + 1] < off[r] || off[0] != 0) HDB_THROW(HDB_EINVAL, "merge_sorted_runs: bad run offsets");
         const int64_t ne = off.back();

@@ -71,8 +71,8 @@ struct hdb_ctx {
     int64_t knn_tree_min_n = 8192;
     bool knn_mfma = true;           // K1m for euclidean lists with 16 < d <= 256
     int64_t knn_mfma_min_n = 2048;
-    bool knn_mfma_two_pass = true;  // K1m two-pass kernel (fallback): upper-bound pass first (few exact re-checks)
     bool knn_mfma_single = true;    // K1m single pass: screen + candidate log, FP64 re-check of the log
+                                    // (false, or a log overflow: the two-pass kernel, upper-bound pass first)
     bool knn_mfma_prune = true;     // K1m single pass: k-means order + FP64-ball superblock pruning
     bool nearest_grouped = true;   // K3g: median-split sample groups + box pruning for big unkeyed scans
     bool boruvka_seed = true;      // seed Boruvka rounds from the previous round's edges
@@ -101,11 +101,11 @@ struct hdb_ctx {
     int flat_link_variant = 1;  // K6 dc_link A/B: 0 direct guarded atomics, 1 LDS-combined multi-batch
     int flat_root_variant = 3;  // K6 dc_root A/B: 0 LDS table (256 threads), 1 (1024), 2 direct atomics, 3-5 multi-batch
     bool flat_relabel = true;  // K6: divide-and-conquer vertex labels in rank order (locality; false: point ids)
-    int flat_block_log = 10;
-    int flat_mid_log = 12;     // K6: depths below 2^flat_mid_log ranks per workgroup (dc_mid, L2-local); <= block log: off
+    int flat_block_log = 10;   // K6: deep depths per workgroup in LDS (2^x ranks, 8-10; 0: the sequential dc_local)
+    int flat_mid_log = 12;    // K6: depths below 2^flat_mid_log ranks per workgroup (dc_mid, L2-local); <= block log: off
     int flat_deep_depth = 64;  // K6: global depths >= this use flat_deep_root / flat_deep_link (A/B)
     int flat_deep_root = 3;
-    int flat_deep_link = 1;   // K6: deep depths per workgroup in LDS (2^x ranks, 8-10; 0: the sequential dc_local)
+    int flat_deep_link = 1;
     bool ssort = true;         // sample sort (ssort.hpp) for the Morton order, the edge orders and K6's term sort
                                // (false: the rocPRIM radix chains; A/B and tests)
     int ssort_cap = 0;         // ssort bucket size sorted in LDS (0: SS_CAP; tests lower it to run the merge path)

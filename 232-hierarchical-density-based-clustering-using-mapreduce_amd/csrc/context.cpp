@@ -353,10 +353,6 @@ int hdb_ctx_set_option(hdb_ctx *ctx, const char *name, int64_t value) {
         ctx->knn_mfma = value != 0;
         return HDB_OK;
     }
-    if (k == "knn_mfma_two_pass") {
-        ctx->knn_mfma_two_pass = value != 0;
-        return HDB_OK;
-    }
     if (k == "nearest_grouped") {
         ctx->nearest_grouped = value != 0;
         return HDB_OK;
@@ -467,6 +463,26 @@ int hdb_ctx_set_option(hdb_ctx *ctx, const char *name, int64_t value) {
     if (k == "flat_mid_log") {
         if (value < 0 || value > 24) return HDB_EINVAL;
         ctx->flat_mid_log = (int)value;
+        return HDB_OK;
+    }
+    if (k == "flat_block_log") {
+        if (value != 0 && (value < 8 || value > 10)) return HDB_EINVAL;
+        ctx->flat_block_log = (int)value;
+        return HDB_OK;
+    }
+    if (k == "flat_root_variant" || k == "flat_deep_root") {
+        if (value < 0 || value > 5) return HDB_EINVAL;
+        (k == "flat_root_variant" ? ctx->flat_root_variant : ctx->flat_deep_root) = (int)value;
+        return HDB_OK;
+    }
+    if (k == "flat_link_variant" || k == "flat_deep_link") {
+        if (value < 0 || value > 1) return HDB_EINVAL;
+        (k == "flat_link_variant" ? ctx->flat_link_variant : ctx->flat_deep_link) = (int)value;
+        return HDB_OK;
+    }
+    if (k == "flat_deep_depth") {
+        if (value < 0 || value > 64) return HDB_EINVAL;
+        ctx->flat_deep_depth = (int)value;
         return HDB_OK;
     }
     if (k == "flat_relabel") {

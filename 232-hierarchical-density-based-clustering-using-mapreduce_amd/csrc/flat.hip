@@ -1156,7 +1156,7 @@ __global__ void fo_paths_init(const int32_t *__restrict__ cpar, const int32_t *_
         const bool heavy = p >= 0 && p < K && pk_lo(hkey[p]) == (int32_t)c;
         jw[c] = heavy ? pk(p, 1) : pk((int32_t)c, 0);
         const int32_t k = nch[c];
-        if (k > 2) {  // insertion sort by smallest id (few, small segments)
+        if (k > 2 && k <= 16) {  // insertion sort by smallest id (few, small segments)
             int32_t *s = kids + kstart[c];
             for (int32_t i = 1; i < k; i++) {
                 const int32_t x = s[i], key = cmin[x];
@@ -1166,6 +1166,37 @@ __global__ void fo_paths_init(const int32_t *__restrict__ cpar, const int32_t *_
                     j--;
                 }
                 s[j + 1] = x;
+            }
+        } else if (k > 16) {
+            // a tied hub: thousands of children of one node (a 40,000-edge tree with four distinct
+            // weights spent 200 ms here, 99 % of the call, in the quadratic sort above).  The keys
+            // are distinct, so a heapsort gives the same order in O(k log k)
+            int32_t *s = kids + kstart[c];
+            auto sift = [&](int32_t root, int32_t end) {  // max-heap on cmin over s[0 .. end)
+                const int32_t x = s[root], key = cmin[x];
+                while (true) {
+                    int32_t ch = 2 * root + 1;
+                    if (ch >= end) break;
+                    int32_t kc = cmin[s[ch]];
+                    if (ch + 1 < end) {
+                        const int32_t k2 = cmin[s[ch + 1]];
+                        if (k2 > kc) {
+                            ch++;
+                            kc = k2;
+                        }
+                    }
+                    if (kc <= key) break;
+                    s[root] = s[ch];
+                    root = ch;
+                }
+                s[root] = x;
+            };
+            for (int32_t i = k / 2 - 1; i >= 0; i--) sift(i, k);
+            for (int32_t e = k - 1; e > 0; e--) {
+                const int32_t t = s[0];
+                s[0] = s[e];
+                s[e] = t;
+                sift(0, e);
             }
         }
     }
@@ -1715,6 +1746,8 @@ void flat_labels_device(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, cons
     const int LB = ctx->flat_block_log >= 8 && ctx->flat_block_log <= 10 ? ctx->flat_block_log : LOC_LOG;
     // depths LM-1 .. LB per workgroup (dc_mid), the shallower ones global
     const int LM = ctx->flat_mid_log > LB ? std::max(LB, std::min(ctx->flat_mid_log, J)) : LB;
+    ctx->stats["flat_global_depths"] = std::max(0, J - LM);  // what this call runs (tests of the variants)
+    ctx->stats["flat_mid_depths"] = LM - LB;
     for (int j = 0; j < J - LM; j++) {
         const int b = J - 1 - j;
         // L ranks (bit b clear) below m; every U rank is an L rank + 2^b

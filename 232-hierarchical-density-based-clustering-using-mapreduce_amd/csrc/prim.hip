@@ -1206,6 +1206,8 @@ static bool launch_coop4_bs(hdb_ctx *ctx, const PrimIn &in, int64_t o, int64_t n
         if (!h_err) {
             ctx->stats["prim_coop_steps"] += n - 1;  // sequential Prim steps (roofline: bench.py)
             ctx->stats["prim_coop_launches"] += 1;
+            ctx->stats["prim_coop_last_bs"] = BS;  // what the last cooperative Prim ran with (tests)
+            ctx->stats["prim_coop_last_spread"] = attempt == 0 ? spread : 1;
             return true;
         }
         if (attempt == 0) ctx->stats["prim_coop_plain_retries"] += 1;

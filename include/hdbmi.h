@@ -81,8 +81,9 @@ int hdb_ctx_synchronize(hdb_ctx *ctx);
  *   "knn_mfma"        (default 1): euclidean lists with 16 < d <= 256 and n >= "knn_mfma_min_n"
  *                                  (default 2048) use K1m (bf16-split MFMA screen, FP64 re-check);
  *                                  "knn_mfma_single" (1: one screen pass + candidate log; 0: the
- *                                  two-pass kernel, "knn_mfma_two_pass"), "knn_mfma_prune" (1:
- *                                  k-means order + FP64-ball superblock pruning);
+ *                                  two-pass kernel, which is also what a call falls back to when a
+ *                                  query's candidate log overflows: stat "knn_mfma_log_overflow"),
+ *                                  "knn_mfma_prune" (1: k-means order + FP64-ball superblock pruning);
  *   "nearest_grouped" (default 1): K3g (median-split sample groups, box pruning) for large
  *                                  euclidean nearest-sample scans;
  *   "prim_coop"       (default 1): single-launch cooperative Prim for 4096 < n <= 65536;
@@ -124,6 +125,16 @@ int hdb_ctx_synchronize(hdb_ctx *ctx);
  *                                  (locality of the label records; the labels are unchanged);
  *   "flat_mid_log"    (default 12): hdb_flat_labels runs the divide-and-conquer depths below
  *                                  2^flat_mid_log ranks per workgroup (<= 10: all global);
+ *                                  "flat_block_log" (default 10; 8..10: the 2^x-rank blocks the
+ *                                  deepest depths run in LDS, 0: the sequential 256-rank kernel),
+ *                                  "flat_root_variant" (0..5, default 3) / "flat_link_variant"
+ *                                  (0..1, default 1): the kernels of the global depths (A/B);
+ *                                  "flat_deep_depth" (default 64): global depths >= it use
+ *                                  "flat_deep_root" / "flat_deep_link" instead; stats
+ *                                  "flat_global_depths" / "flat_mid_depths" of the last call;
+ *   "prim_coop_bs"    (default 1024; 0, 128..1024): cooperative Prim workgroup size, 0 = the
+ *                                  smallest that keeps the Prim within 32 workgroups; stats
+ *                                  "prim_coop_last_bs" / "prim_coop_last_spread" of the last one;
  *   "count_evals"     (default 0): K1t/K2b count the pairs they evaluate (read "last_evals"). */
 int hdb_ctx_set_option(hdb_ctx *ctx, const char *name, int64_t value);
 /* Diagnostic counters: "last_evals" = pair evaluations of the last K1t call (count_evals on). */
@@ -236,12 +247,13 @@ int hdb_bubble_prim_mst(hdb_ctx *ctx, const double *rep, const double *eB, const
  * 0..b-1: bubble cores, bubble Prim, UndirectedGraph.quicksortByEdgeWeight, cluster tree,
  * FOSC + noise reassignment, inter-cluster edges.  info = b*3 (extent, nnDist, n).
  * Outputs: labels[b]; mst_* (2b-1, quicksorted ascending, nullable); ic_* (capacity 2b-1),
- * *n_ic = number of inter-cluster edges.  Host memory only for outputs. */
+ * *n_ic = number of inter-cluster edges.  rep and info may be host or device memory; the
+ * outputs (labels, mst_*, ic_*, n_ic) are host memory only: HDB_EINVAL for a device pointer. */
 int hdb_local_model(hdb_ctx *ctx, const double *rep, const double *info, int64_t b, int32_t d, int32_t min_pts,
                     int32_t min_cl_size, int32_t metric, int32_t *labels, int32_t *mst_va, int32_t *mst_vb,
                     double *mst_w, int32_t *ic_va, int32_t *ic_vb, double *ic_w, int64_t *n_ic);
 
-/* hdb_local_model from precomputed bubble core distances (host, b values: hdb_bubble_core_distances
+/* hdb_local_model from precomputed bubble core distances (host or device, b values: hdb_bubble_core_distances
  * of the same rep / nB = (int) info[:, 2] / eB = info[:, 0] / nnB = info[:, 1], min_pts, metric) --
  * the same outputs; lets a caller compute every model's cores of a level before any model's Prim
  * (round 6: a Prim holds its CUs for its whole run and slows concurrent work). */
@@ -266,7 +278,8 @@ int hdb_sort_edges_desc(hdb_ctx *ctx, int32_t *va, int32_t *vb, double *w, int64
  * stable sort of a rank-major concatenation of raw lists equals this merge of the ranks'
  * individually sorted lists, so a reducer merges instead of re-sorting (pairwise merge-path
  * tiles, O(E log nruns)).  Outputs must not alias inputs.  HDB_EINVAL on a NaN weight or a
- * run that is not descending.  Synchronises. */
+ * run that is not descending.  run_off (nruns + 1 values) may be host or device memory like
+ * the other arrays.  Synchronises. */
 int hdb_merge_sorted_runs(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, const double *w, const int64_t *run_off,
                           int32_t nruns, int32_t *oa, int32_t *ob, double *ow);
 

@@ -664,14 +664,8 @@ def _coop_slots_case(pkg, oracle, d, metric, n):
     assert eq(mst.getVerticeA(), ra) and eq(mst.getVericeB(), rb) and eq(mst.getEges(), rw)
 
 
-@pytest.mark.parametrize("case", ["ties", "descending"])
-def test_bubble_core_split_scan_vs_oracle(pkg, oracle, case):
-    """K5 in candidate chunks with the exact event replay (bubbles.hip): the bubble core
-    distances -- which read the sequential scan's per-position insertion log through the stale
-    indexBubbles epilogue (HdbscanDataBubbles.java:121-143) -- equal the oracle's on 9,000
-    bubbles with massive distance ties (rounded coordinates, repeated extents), and on a 1-D
-    descending layout where every candidate is a new nearest for the far points (the chunks'
-    event buffers overflow and the sequential scan takes over)."""
+def split_scan_case(case):
+    """9,000 bubbles: massive distance ties, or a 1-D descending layout (see the test below)"""
     rng = np.random.default_rng(31)
     n = 9000
     if case == "ties":
@@ -683,9 +677,29 @@ def test_bubble_core_split_scan_vs_oracle(pkg, oracle, case):
         eB = np.full(n, 0.1)
         nnB = np.full(n, 0.05)
     nB = rng.integers(1, 9, n).astype(np.int32)
+    return X, nB, eB, nnB
+
+
+@pytest.mark.parametrize("case", ["ties", "descending"])
+def test_bubble_core_split_scan_vs_oracle(pkg, oracle, case):
+    """K5 in candidate chunks with the exact event replay (bubbles.hip): the bubble core
+    distances -- which read the sequential scan's per-position insertion log through the stale
+    indexBubbles epilogue (HdbscanDataBubbles.java:121-143) -- equal the oracle's on 9,000
+    bubbles with massive distance ties (rounded coordinates, repeated extents), and on a 1-D
+    descending layout where every candidate is a new nearest for the far points (the chunks'
+    event buffers overflow and the sequential scan takes over: the overflow stat must say so,
+    and must stay put on the ties).  The candidates are split only while a chunk of >= 256
+    of them is expected to stay within half its event buffer, K e^(32 / K - 1) >= 256
+    (bubble_knn_launch): K = minPts - 1 <= 6, so minPts 8 takes the plain scan directly."""
+    X, nB, eB, nnB = split_scan_case(case)
     model = pkg.HdbscanDataBubbles()
-    for k in (4, 8):
+    ctx = pkg.Context.get(0)  # the context the model above runs on
+    for k in (4, 7, 8):
+        split = (k - 1) * np.exp(32.0 / (k - 1) - 1.0) >= 256.0
+        before = ctx.get_stat("bubble_knn_replay_overflows")
         core = model.calculateCoreDistancesBubbles(X, nB, eB, nnB, k)
+        grew = ctx.get_stat("bubble_knn_replay_overflows") - before
+        assert grew == (1 if case == "descending" and split else 0), (case, k, grew)
         assert eq(core, oracle.bubble_core_distances(X, nB, eB, nnB, k)), (case, k)
 
 

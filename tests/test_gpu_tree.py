@@ -28,7 +28,8 @@ def eq(a, b):
 def options(ctx, **kw):
     defaults = {"knn_tree": 1, "knn_tree_min_n": 8192, "knn_fp32_screen": 1, "count_evals": 0,
                 "leaf_seed_k": -1, "leaf_list_rounds": 2, "boruvka_seed": 1, "boruvka_wave_pts": 64,
-                "boruvka_early_pts": 0, "boruvka_adj_seed": 1, "k1t_xcd_chunks": 8, "bor_xcd_chunks": 8}
+                "boruvka_early_pts": 0, "boruvka_adj_seed": 1, "k1t_xcd_chunks": 8, "bor_xcd_chunks": 8,
+                "trav_pop_test": 0, "boruvka_knn_seed": 1, "boruvka_early_rounds": 5}
     try:
         for k, v in kw.items():
             ctx.set_option(k, v)
@@ -189,6 +190,7 @@ def test_exact_mst_ragged(star, oracle, n):
     assert len(g.getEges()) == 2 * n - 1
     _, _, w = oracle.prim_mst(X, core, self_edges=False)
     assert eq(np.sort(g.getEges()[: n - 1]), np.sort(w))
+    assert _spanning_tree(g.getVerticeA()[: n - 1], g.getVericeB()[: n - 1], n)
 
 
 def test_exact_mst_device_full_size(star):
@@ -221,7 +223,13 @@ def test_exact_mst_seeding_options_equal(ctx, star, d):
                # the diagnostic pass at its largest per-wave record count (the
                # record buffer must fit its carve at 16 points per wave)
                dict(count_evals=1, boruvka_wave_pts=16, boruvka_early_pts=16),
-               dict(count_evals=1, boruvka_wave_pts=32)):
+               dict(count_evals=1, boruvka_wave_pts=32),
+               # no list seeds at all; the early rounds' wave size on no round, on two, on five
+               dict(boruvka_knn_seed=0), dict(boruvka_knn_seed=0, boruvka_seed=0, boruvka_adj_seed=0),
+               dict(boruvka_early_rounds=0, boruvka_early_pts=16), dict(boruvka_early_rounds=2, boruvka_early_pts=16),
+               dict(boruvka_early_rounds=2, boruvka_early_pts=32), dict(boruvka_early_pts=32),
+               # popped nodes re-tested against the tightened bound (Boruvka, K1t, both)
+               dict(trav_pop_test=1), dict(trav_pop_test=2), dict(trav_pop_test=3)):
         with options(ctx, **kw):
             c2, g = star.exactMST(X, 4, None, 2, selfEdges=False)
         assert eq(c2, core), kw
