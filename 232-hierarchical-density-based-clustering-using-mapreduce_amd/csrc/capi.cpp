@@ -544,4 +544,33 @@ int hdb_flat_labels(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, const do
     });
 }
 
+int hdb_flat_outlier_scores(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, const double *w, int64_t ne, int64_t n,
+                            int32_t min_cl_size, double *scores, double *noise_level, int32_t *labels,
+                            int64_t *n_clusters) {
+    if (!ctx) {  // host-only use (all pointers in host memory): no device needed
+        try {
+            if (ne < 0 || n < 0 || (ne > 0 && (!va || !vb || !w)) || (n > 0 && !scores))
+                HDB_THROW(HDB_EINVAL, "bad arguments");
+            return flat_outlier_scores_host(va, vb, w, ne, n, min_cl_size, scores, noise_level, labels, n_clusters);
+        } catch (const Error &e) {
+            set_error(e.msg);
+            return e.code;
+        } catch (const std::bad_alloc &) {
+            set_error("host allocation failed");
+            return HDB_ENOMEM;
+        }
+    }
+    return guarded(ctx, [&] {
+        if (ne < 0 || n < 0 || (ne > 0 && (!va || !vb || !w)) || (n > 0 && !scores)) HDB_THROW(HDB_EINVAL, "bad arguments");
+        Stager sg(ctx);
+        const int32_t *da = sg.in(va, (size_t)ne), *db = sg.in(vb, (size_t)ne);
+        const double *dw = sg.in(w, (size_t)ne);
+        const size_t np = (size_t)std::max<int64_t>(n, 0);
+        double *ds = sg.out(scores, np), *dn = sg.out(noise_level, np);
+        int32_t *dl = sg.out(labels, np);
+        flat_outlier_scores_device(ctx, da, db, dw, ne, n, min_cl_size, ds, dn, dl, n_clusters);
+        sg.finish();
+    });
+}
+
 }  // extern "C"

@@ -13,9 +13,13 @@
 //   2. one top-down pass over the dendrogram condenses it (valid child = >= minClSize points)
 //      and accumulates each cluster's stability in descending level order, exactly the
 //      order the top-down Java visits them;
-//   3. FOSC propagation children-before-parents, then one pass labels the points.
+//   3. FOSC propagation children-before-parents, then one pass labels the points;
+//   4. on request, the GLOSH outlier scores (HDBSCANStar.java:505-540, 653-686): step 2 records
+//      where each point leaves and each cluster's lowest level, one pass children-before-parents
+//      propagates the levels, one pass scores the points.
 // O(E log E + n) host work; the inputs may live in HBM (staged once).
 #include <algorithm>
+#include <limits>
 #include <numeric>
 #include <vector>
 
@@ -53,10 +57,10 @@ struct Clu {
     std::vector<int32_t> kids;  // ascending minid
 };
 
-}  // namespace
-
-int flat_labels_host(const int32_t *va, const int32_t *vb, const double *w, int64_t ne, int64_t n, int32_t mcs,
-                     int32_t *labels, int64_t *n_clusters) {
+// labels / n_clusters: the flat partition (labels nullable).  scores / noise (nullable): GLOSH
+// outlier scores and eps(x) from the same hierarchy (see flat_outlier_scores_host below).
+int flat_host_impl(const int32_t *va, const int32_t *vb, const double *w, int64_t ne, int64_t n, int32_t mcs,
+                   int32_t *labels, int64_t *n_clusters, double *scores, double *noise) {
     if (n <= 0) {
         if (n_clusters) *n_clusters = 0;
         return HDB_OK;
@@ -139,6 +143,17 @@ int flat_labels_host(const int32_t *va, const int32_t *vb, const double *w, int6
     std::vector<std::pair<int32_t, int32_t>> stack;  // (node, cluster)
     if (n > 1) stack.push_back({root, 0});
     std::vector<int32_t> valid;
+    // outlier scores: a point leaves (becomes noise) at the reached node whose invalid child
+    // holds it -- eps(x) = that node's level, last(x) = that node's cluster; a cluster's own
+    // lowest level is the level of the last node on its chain (levels fall along it)
+    const bool want_scores = scores != nullptr;
+    std::vector<double> eps_pt, death;
+    std::vector<int32_t> last_pt, sub;
+    if (want_scores) {
+        eps_pt.assign((size_t)n, 0.0);
+        last_pt.assign((size_t)n, 0);
+        death.assign(1, 0.0);
+    }
     while (!stack.empty()) {
         auto [x, L] = stack.back();
         stack.pop_back();
@@ -148,8 +163,27 @@ int flat_labels_host(const int32_t *va, const int32_t *vb, const double *w, int6
         int64_t invalid_pts = 0;
         for (int32_t k = 0; k < X.n_children; k++) {
             int32_t c = pool[X.first_child + k];
-            if (nodes[c].size >= mcs) valid.push_back(c);
-            else invalid_pts += nodes[c].size;
+            if (nodes[c].size >= mcs) {
+                valid.push_back(c);
+                continue;
+            }
+            invalid_pts += nodes[c].size;
+            if (!want_scores) continue;
+            sub.assign(1, c);  // every point below an invalid child leaves here
+            while (!sub.empty()) {
+                const int32_t y = sub.back();
+                sub.pop_back();
+                if (y < n) {
+                    eps_pt[y] = eps;
+                    last_pt[y] = L;
+                    continue;
+                }
+                for (int32_t q = 0; q < nodes[y].n_children; q++) sub.push_back(pool[nodes[y].first_child + q]);
+            }
+        }
+        if (want_scores) {
+            death.resize(cl.size() + (valid.size() >= 2 ? valid.size() : 0), 0.0);
+            death[L] = eps;  // descending along the chain: the last write is the lowest
         }
         const double inv_birth = 1.0 / cl[L].birth;
         if (valid.size() >= 2) {
@@ -191,9 +225,9 @@ int flat_labels_host(const int32_t *va, const int32_t *vb, const double *w, int6
         else todo.insert(todo.end(), cl[c].kids.begin(), cl[c].kids.end());
     }
     std::sort(sel.begin(), sel.end(), [&](int32_t a, int32_t b) { return cl[a].minid < cl[b].minid; });
-    std::fill(labels, labels + n, 0);
+    if (labels) std::fill(labels, labels + n, 0);
     std::vector<int32_t> dfs;
-    for (size_t i = 0; i < sel.size(); i++) {
+    for (size_t i = 0; labels && i < sel.size(); i++) {
         dfs.assign(1, cl[sel[i]].node);
         while (!dfs.empty()) {
             int32_t x = dfs.back();
@@ -206,7 +240,36 @@ int flat_labels_host(const int32_t *va, const int32_t *vb, const double *w, int6
         }
     }
     if (n_clusters) *n_clusters = (int64_t)sel.size();
+
+    // ---- 4. GLOSH: eps_max(C) = the lowest level among C and its descendants
+    // (Cluster.propagate's propagatedLowestChildDeathLevel, Cluster.java:99-105); the root
+    // takes its descendants only and keeps Double.MAX_VALUE when it never splits
+    if (want_scores) {
+        std::vector<double> eps_max(death);
+        eps_max[0] = std::numeric_limits<double>::max();
+        for (int64_t c = nc - 1; c >= 1; c--) eps_max[cl[c].parent] = std::min(eps_max[cl[c].parent], eps_max[c]);
+        for (int64_t v = 0; v < n; v++) {  // n == 1: no level at all, eps = 0
+            const double e = eps_pt[v];
+            scores[v] = e == 0.0 ? 0.0 : 1.0 - eps_max[last_pt[v]] / e;  // calculateOutlierScores :662-667
+            if (noise) noise[v] = e == 0.0 ? 0.0 : e;  // a -0.0 level is reported as 0.0, as the device does
+        }
+    }
     return HDB_OK;
+}
+
+}  // namespace
+
+int flat_labels_host(const int32_t *va, const int32_t *vb, const double *w, int64_t ne, int64_t n, int32_t mcs,
+                     int32_t *labels, int64_t *n_clusters) {
+    return flat_host_impl(va, vb, w, ne, n, mcs, labels, n_clusters, nullptr, nullptr);
+}
+
+// GLOSH outlier scores (HDBSCANStar.propagateTree :505-540 + calculateOutlierScores :653-686)
+// over the hierarchy above: score(x) = eps(x) == 0 ? 0 : 1 - eps_max(last(x)) / eps(x).
+// labels, n_clusters and noise (eps per point) are optional outputs of the same pass.
+int flat_outlier_scores_host(const int32_t *va, const int32_t *vb, const double *w, int64_t ne, int64_t n,
+                             int32_t mcs, double *scores, double *noise, int32_t *labels, int64_t *n_clusters) {
+    return flat_host_impl(va, vb, w, ne, n, mcs, labels, n_clusters, scores, noise);
 }
 
 }  // namespace hdb

@@ -25,7 +25,10 @@
 //     children; pointer jumping (path halving) finds each node's cluster;
 //  4. per-cluster stability = sequential sum of its chain's terms in descending level (one
 //     radix sort groups the chains); FOSC over the (few) clusters on the host; labels by
-//     pointer jumping to the nearest selected ancestor.
+//     pointer jumping to the nearest selected ancestor;
+//  5. on request (hdb_flat_outlier_scores), the GLOSH outlier scores from the same arrays:
+//     first valid ancestor per node (pointer jumping), each cluster's own lowest level (one
+//     store), subtree minima over the cluster tree (exact pointer doubling), a per-point pass.
 #include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
@@ -1601,6 +1604,138 @@ __global__ void fl_point_labels(const int32_t *__restrict__ pparent, const int32
     HDB_GRID_STRIDE(v, n) labels[v] = clab[cid[cs[top[pparent[v]]]]];
 }
 
+// ------------------------------------------------------------------ 6. outlier scores (GLOSH)
+// HDBSCANStar.propagateTree :505-540 / calculateOutlierScores :653-686 over the arrays above
+// (run only when scores are asked for).  eps(x) = the level of x's first valid ancestor node
+// (>= minClSize points, or the root); last(x) = that node's cluster = cs[top[pparent[x]]] (cs
+// already jumps through the invalid nodes); eps_max(C) = the lowest level at which C or a
+// descendant cluster ends (Cluster.propagate :99-105), for the root its descendants only, from
+// Double.MAX_VALUE.  Only exact operations (min, one division, one subtraction): the host's bits.
+
+// doubles as unsigned keys of the same order (weights may be negative), for integer atomic min
+__device__ __forceinline__ unsigned long long ord_enc(double x) {
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double ord_dec(unsigned long long k) {
+    return __builtin_bit_cast(double, (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k);
+}
+__device__ __forceinline__ unsigned long long u64_ld(const unsigned long long *p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// first valid ancestor: an upward forest over the nodes, r -> r when r is valid or the root,
+// else r -> its parent node; chains have at most minClSize - 1 hops (fl_jump resolves it)
+__global__ void gl_fva_init(const int32_t *__restrict__ top, const int32_t *__restrict__ pnode,
+                            const int32_t *__restrict__ esize, int64_t m, int32_t mcs, int32_t *__restrict__ fva,
+                            unsigned long long *__restrict__ groot, const int *__restrict__ bad) {
+    if (*bad & (FE_CYCLE | FE_ROOTS)) return;  // malformed input: reported by the caller
+    if (blockIdx.x == 0 && threadIdx.x == 0) *groot = ord_enc(DBL_MAX);  // a root that never splits keeps it
+    HDB_GRID_STRIDE(r, m) {
+        int32_t u = (int32_t)r;
+        if (top[r] == (int32_t)r && esize[r] < mcs) {
+            const int32_t P = pnode[r];
+            if (P != NONE) u = P;
+        }
+        fva[r] = u;
+    }
+}
+
+// Own lowest level per cluster.  The reached nodes of a cluster form one chain of strictly
+// falling levels (a node with exactly one valid child hands its cluster to that child), so the
+// minimum over the chain is the level of its last node, the one whose valid-child count is not
+// 1: one plain store per cluster, no atomics.  dw[c] holds it as an ordered key (the subtree
+// pass below takes integer minima).  The root's eps_max is the minimum over every other
+// cluster: combined per workgroup, one atomic per workgroup (groot starts at Double.MAX_VALUE).
+// up[c] = the parent cluster, or -1 for the root and its children (nothing propagates into or
+// out of the root here).
+__global__ void gl_own_level(const int32_t *__restrict__ top, const int32_t *__restrict__ pnode,
+                             const int32_t *__restrict__ esize, const int32_t *__restrict__ nvalid,
+                             const int32_t *__restrict__ cs, const int32_t *__restrict__ cid,
+                             const int32_t *__restrict__ cpar, const int32_t *__restrict__ Kp,
+                             const double *__restrict__ ew, int64_t m, int32_t mcs,
+                             unsigned long long *__restrict__ dw, int32_t *__restrict__ up,
+                             unsigned long long *__restrict__ groot, const int *__restrict__ bad) {
+    if (*bad & (FE_CYCLE | FE_ROOTS)) return;  // malformed input: reported by the caller
+    __shared__ unsigned long long smin;
+    if (threadIdx.x == 0) smin = ~0ull;
+    __syncthreads();
+    const int32_t K = *Kp;
+    unsigned long long mine = ~0ull;
+    HDB_GRID_STRIDE(r, m) {
+        if (top[r] != (int32_t)r) continue;
+        const bool root = pnode[r] == NONE;
+        if (!(root || esize[r] >= mcs) || nvalid[r] == 1) continue;  // not reached / not its chain's end
+        const int32_t c = cid[cs[r]];
+        if ((uint32_t)c >= (uint32_t)K) continue;
+        const unsigned long long k = ord_enc(ew[r]);
+        dw[c] = k;
+        if (c != K - 1) mine = k < mine ? k : mine;
+    }
+    HDB_GRID_STRIDE(c, K) {
+        const int32_t p = c == K - 1 ? -1 : cpar[c];
+        up[c] = (p < 0 || p >= K - 1) ? -1 : p;
+    }
+    for (int o = 32; o >= 1; o >>= 1) {
+        const unsigned long long other = __shfl_xor(mine, o);
+        mine = other < mine ? other : mine;
+    }
+    if ((threadIdx.x & 63) == 0 && mine != ~0ull) atomicMin(&smin, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && smin != ~0ull) atomicMin(groot, smin);
+}
+
+// Subtree minima over the cluster tree by exact pointer doubling.  Before round k, up_in[c] is
+// c's 2^k-th ancestor (-1: none below the root) and dw[c] <= every own level within 2^k - 1
+// steps below c.  The round folds dw[c] into dw[up_in[c]] (integer atomic min, read first: most
+// see their bound already met) and writes the 2^(k+1)-th ancestor to up_out: a descendant d of
+// a at distance D in [2^k, 2^(k+1)) reaches a through its ancestor at distance exactly 2^k
+// from a.  min is idempotent and dw only ever holds levels of c's subtree, so reading a dw
+// that this round already lowered is harmless; the ancestors are double-buffered, so each
+// round doubles exactly.  flag_next: some ancestor is still live.
+__global__ void gl_subtree_min(unsigned long long *__restrict__ dw, const int32_t *__restrict__ up_in,
+                               int32_t *__restrict__ up_out, const int32_t *__restrict__ Kp,
+                               const int *__restrict__ flag_prev, int *__restrict__ flag_next,
+                               const int *__restrict__ bad) {
+    if (*bad & (FE_CYCLE | FE_ROOTS)) return;  // malformed input: reported by the caller
+    if (flag_prev && *flag_prev == 0) return;
+    const int32_t K = *Kp;
+    int ch = 0;
+    HDB_GRID_STRIDE(c, K) {
+        const int32_t a = up_in[c];
+        int32_t a2 = -1;
+        if (a >= 0) {
+            const unsigned long long v = u64_ld(dw + c);
+            if (u64_ld(dw + a) > v) atomicMin(dw + a, v);
+            a2 = up_in[a];
+            if (a2 >= 0) ch = 1;
+        }
+        up_out[c] = a2;
+    }
+    flag_or(flag_next, ch);
+}
+
+// per point: score and noise level (two coalesced 8-byte stores), and the label when wanted
+__global__ void gl_point_scores(const int32_t *__restrict__ pparent, const int32_t *__restrict__ top,
+                                const int32_t *__restrict__ fva, const int32_t *__restrict__ cs,
+                                const int32_t *__restrict__ cid, const int32_t *__restrict__ clab,
+                                const double *__restrict__ ew, const unsigned long long *__restrict__ dw,
+                                const unsigned long long *__restrict__ groot, const int32_t *__restrict__ Kp,
+                                int64_t n, double *__restrict__ scores, double *__restrict__ noise,
+                                int32_t *__restrict__ labels, const int *__restrict__ bad) {
+    if (*bad & (FE_CYCLE | FE_ROOTS)) return;  // malformed input: reported by the caller
+    const int32_t K = *Kp;
+    HDB_GRID_STRIDE(v, n) {
+        const int32_t t = top[pparent[v]];
+        const double eps = ew[fva[t]];
+        const int32_t c = cid[cs[t]];
+        const double eps_max = ord_dec(c == K - 1 ? *groot : dw[c]);
+        scores[v] = eps == 0.0 ? 0.0 : 1.0 - eps_max / eps;  // calculateOutlierScores :662-667
+        if (noise) noise[v] = eps;
+        if (labels) labels[v] = clab[c];
+    }
+}
+
 // zero-initialised FOSC block: nch, kcur, plen, maxld (+ counters), pwide, a spare (m ints
 // each: 24m bytes, so the u64 array after them is 8-byte aligned), hkey (m u64), 192 jump flags
 inline size_t fz_layout(int64_t m) { return (size_t)m * 24 + (size_t)m * 8 + 192 * 4; }
@@ -1620,8 +1755,11 @@ struct Carver {
 
 }  // namespace
 
-void flat_labels_device(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, const double *w, int64_t ne, int64_t n,
-                        int32_t mcs, int32_t *labels, int64_t *n_clusters) {
+// labels-only (scores == nullptr: exactly the launches of K6) or with the outlier-score passes
+// of section 6 after them; labels and noise are nullable when scores are given
+static void flat_device_impl(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, const double *w, int64_t ne,
+                             int64_t n, int32_t mcs, int32_t *labels, int64_t *n_clusters, double *scores,
+                             double *noise) {
     if (n <= 0) {
         if (n_clusters) *n_clusters = 0;
         return;
@@ -1707,7 +1845,9 @@ void flat_labels_device(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, cons
     if (e0 & FE_NAN) HDB_THROW(HDB_EINVAL, "flat labels: NaN edge weight");
     if (m_got != m) HDB_THROW(HDB_EINVAL, "flat labels: the edges are not a spanning tree");
     if (m == 0) {  // one point: no hierarchy below the root
-        HIP_CHECK(hipMemsetAsync(labels, 0, sizeof(int32_t), st));
+        if (labels) HIP_CHECK(hipMemsetAsync(labels, 0, sizeof(int32_t), st));
+        if (scores) HIP_CHECK(hipMemsetAsync(scores, 0, sizeof(double), st));  // no level: eps = 0, score 0
+        if (noise) HIP_CHECK(hipMemsetAsync(noise, 0, sizeof(double), st));
         if (n_clusters) *n_clusters = 0;
         return;
     }
@@ -1815,7 +1955,7 @@ void flat_labels_device(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, cons
     double *stab = cv2.take<double>(m);
     int32_t *cpar = cv2.take<int32_t>(m), *cminid = cv2.take<int32_t>(m), *clab = cv2.take<int32_t>(m);
     int *jflags = cv2.take<int32_t>(64);
-    cv2.take<int64_t>(1);
+    unsigned long long *groot = (unsigned long long *)cv2.take<int64_t>(1);  // outlier scores: the root's eps_max
     int32_t *csz = cv2.take<int32_t>(m), *kstart = cv2.take<int32_t>(m), *kids = cv2.take<int32_t>(m),
             *pnodes = cv2.take<int32_t>(m), *poff = cv2.take<int32_t>(m),
             *ssel = cv2.take<int32_t>(m), *Kp = cv2.take<int32_t>(m), *rc = cv2.take<int32_t>(m),
@@ -1842,22 +1982,22 @@ void flat_labels_device(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, cons
 #define HDB_JUMP_WG 256
 #endif
     const unsigned jump_wg = (unsigned)(HDB_JUMP_WG > 0 ? std::min<int64_t>(g / 4 + 1, HDB_JUMP_WG) : g / 4 + 1);
-    auto jump_all = [&](int32_t *up) {  // roots of an upward forest, in place
+    auto jump_all = [&](int32_t *up, int nr) {  // roots of an upward forest, in place
         HIP_CHECK(hipMemsetAsync(jflags, 0, sizeof(int) * 64, st));
-        for (int k = 0; k < rounds; k++)
+        for (int k = 0; k < nr; k++)
             hipLaunchKernelGGL(fl_jump, dim3(jump_wg), dim3(1024), 0, st, up, m, k ? jflags + k - 1 : nullptr,
                                jflags + k);
-        hipLaunchKernelGGL(fl_jump_check, dim3(1), dim3(64), 0, st, jflags + rounds - 1, err);
+        hipLaunchKernelGGL(fl_jump_check, dim3(1), dim3(64), 0, st, jflags + nr - 1, err);
     };
 
     hipLaunchKernelGGL(fl_tie_up, dim3(g), dim3(256), 0, st, dc.parent, ew, m, top, err);
-    jump_all(top);
+    jump_all(top, rounds);
     HIP_CHECK(hipMemsetAsync(nvalid, 0, sizeof(int32_t) * m, st));
     HIP_CHECK(hipMemsetAsync(vsum, 0, sizeof(int32_t) * m, st));
     NodeArr na{dc.parent, top, dc.esize, pnode, nvalid, vsum, m, mcs};
     hipLaunchKernelGGL(fl_nodes, dim3(g), dim3(256), 0, st, na);
     hipLaunchKernelGGL(fl_starts, dim3(g), dim3(256), 0, st, top, pnode, dc.esize, nvalid, m, mcs, is_start, cs);
-    jump_all(cs);
+    jump_all(cs, rounds);
     {
         size_t tb = 0;
         HIP_CHECK(rocprim::exclusive_scan(nullptr, tb, is_start, cid, 0, (size_t)m, rocprim::plus<int32_t>(), st));
@@ -1945,8 +2085,34 @@ void flat_labels_device(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, cons
     }
     hipLaunchKernelGGL(fo_labels, dim3(g), dim3(256), 0, st, tw, cminid, rk, Kp, clab, err);
     hipLaunchKernelGGL(fo_count, dim3(1), dim3(64), 0, st, mk, rk, n, (int64_t *)(words + 3), err);
-    hipLaunchKernelGGL(fl_point_labels, dim3(grid_for(n)), dim3(256), 0, st, pparent, top, cs, cid, clab, n,
-                       labels, err);
+    if (!scores) {
+        hipLaunchKernelGGL(fl_point_labels, dim3(grid_for(n)), dim3(256), 0, st, pparent, top, cs, cid, clab, n,
+                           labels, err);
+    } else {
+        // ---- 6. outlier scores, in scratch the stability stage is done with (no new footprint):
+        // val1 -> first valid ancestors, val2 -> the two ancestor buffers, key2 -> the level keys
+        int32_t *fva = (int32_t *)val1, *upa = (int32_t *)val2, *upb = upa + m;
+        unsigned long long *dw = (unsigned long long *)key2;
+        hipLaunchKernelGGL(gl_fva_init, dim3(g), dim3(256), 0, st, top, pnode, dc.esize, m, mcs, fva, groot, err);
+        // a chain of invalid nodes has at most minClSize - 1 hops: rounds from that, not from m
+        int frounds = 2;
+        for (int64_t span = 5; span < std::min<int64_t>(mcs, m); span *= 5) frounds++;
+        jump_all(fva, std::min(frounds, 64));
+        hipLaunchKernelGGL(gl_own_level, dim3(g), dim3(256), 0, st, top, pnode, dc.esize, nvalid, cs, cid, cpar, Kp, ew,
+                           m, mcs, dw, upa, groot, err);
+        // the cluster tree below the root's children is at most K - 2 < m deep and a round doubles
+        // exactly: ceil(log2 m) rounds + one, whose flag must be zero
+        int srounds = 2;
+        for (int64_t span = 2; span < m; span *= 2) srounds++;
+        srounds = std::min(srounds, 64);
+        HIP_CHECK(hipMemsetAsync(jflags, 0, sizeof(int) * 64, st));
+        for (int k = 0; k < srounds; k++)
+            hipLaunchKernelGGL(gl_subtree_min, dim3(jump_wg), dim3(1024), 0, st, dw, k & 1 ? upb : upa,
+                               k & 1 ? upa : upb, Kp, k ? jflags + k - 1 : nullptr, jflags + k, err);
+        hipLaunchKernelGGL(fl_jump_check, dim3(1), dim3(64), 0, st, jflags + srounds - 1, err);
+        hipLaunchKernelGGL(gl_point_scores, dim3(grid_for(n)), dim3(256), 0, st, pparent, top, fva, cs, cid, clab, ew,
+                           dw, groot, Kp, n, scores, noise, labels, err);
+    }
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(pin, words, sizeof(int64_t) * 4, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipMemcpyAsync(pin + 4, Kp, sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -1957,6 +2123,18 @@ void flat_labels_device(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, cons
     if (e1 & FE_JUMP) HDB_THROW(HDB_EDEVICE, "flat labels: pointer jumping did not converge in its launch budget");
     if (n_clusters) *n_clusters = pin[3];
     ctx->stats["flat_clusters_total"] = *(int32_t *)(pin + 4);  // condensed-tree clusters incl. the root
+}
+
+void flat_labels_device(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, const double *w, int64_t ne, int64_t n,
+                        int32_t mcs, int32_t *labels, int64_t *n_clusters) {
+    flat_device_impl(ctx, va, vb, w, ne, n, mcs, labels, n_clusters, nullptr, nullptr);
+}
+
+void flat_outlier_scores_device(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, const double *w, int64_t ne,
+                                int64_t n, int32_t mcs, double *scores, double *noise, int32_t *labels,
+                                int64_t *n_clusters) {
+    if (n > 0 && !scores) HDB_THROW(HDB_EINVAL, "bad arguments");
+    flat_device_impl(ctx, va, vb, w, ne, n, mcs, labels, n_clusters, scores, noise);
 }
 
 }  // namespace hdb

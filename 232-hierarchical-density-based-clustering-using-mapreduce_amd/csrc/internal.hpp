@@ -70,12 +70,19 @@ inline bool flat_relabel_fits(int64_t m) { return m >= 0 && 3 * m < (int64_t)INT
 // K6: global hierarchy + flat labels over a merged MST (flat.hip); synchronises
 void flat_labels_device(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, const double *w, int64_t ne, int64_t n,
                         int32_t mcs, int32_t *labels, int64_t *n_clusters);
+// K6 + GLOSH outlier scores from the same hierarchy: scores (n, required), noise (n, eps per
+// point) and labels nullable; synchronises
+void flat_outlier_scores_device(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, const double *w, int64_t ne,
+                                int64_t n, int32_t mcs, double *scores, double *noise, int32_t *labels,
+                                int64_t *n_clusters);
 
 // host logic (local_model.cpp)
 int bubble_core_epilogue(const double *rep, const int32_t *nB, const double *eB, const double *nnB, int64_t b, int d,
                          int min_pts, int metric, const double *knn, const int32_t *log, double *core);
 int flat_labels_host(const int32_t *va, const int32_t *vb, const double *w, int64_t ne, int64_t n, int32_t mcs,
                      int32_t *labels, int64_t *n_clusters);
+int flat_outlier_scores_host(const int32_t *va, const int32_t *vb, const double *w, int64_t ne, int64_t n,
+                             int32_t mcs, double *scores, double *noise, int32_t *labels, int64_t *n_clusters);
 int quicksort_edges(int32_t *va, int32_t *vb, double *w, int64_t ne);
 // message of the last HDB_EREF_NEGATIVE_CLUSTER on this thread (cluster label, level, numPoints)
 const char *local_model_error_detail();

@@ -73,7 +73,7 @@ class MRHDBSCANStar:
                  seed=20210101, distanceFunction=None, all_inter_edges=True, max_levels=64, ctx=None,
                  device=0, flat_labels=True, profile=False, exact_prim_leaves=False, group=None,
                  prim_leaf_max=LEAF_PRIM_MAX, model_threads=4, defer_leaves=True, bubble_slices=BUBBLE_SLICES,
-                 emulate_ranks=(), cores_first=False):
+                 emulate_ranks=(), cores_first=False, outlier_scores=False):
         self.minPts = minPts
         self.minClSize = minClSize
         self.processing_units = processing_units
@@ -86,6 +86,9 @@ class MRHDBSCANStar:
         self.device = device
         self.ctx = ctx
         self.flat_labels = flat_labels
+        # GLOSH outlier scores with the flat labels, from the one hierarchy of a single combined
+        # call (hdb_flat_outlier_scores); needs flat_labels and all_inter_edges
+        self.outlier_scores = outlier_scores
         self.profile = profile       # phase wall times (synchronising) in self.timings
         # True: every leaf, however large, runs the reference Prim (the exact edge list of
         # HDBSCANStar.constructMST, ties included; stepwise above 65,536 points).  False:
@@ -504,8 +507,17 @@ class MRHDBSCANStar:
             # System.exit(1) of Main.java:408); D7 makes the merged edges a spanning tree
             labels = torch.empty(n, dtype=torch.int32, device=dev)
             k = np.zeros(1, np.int64)
-            A.check(A.lib().hdb_flat_labels(c.h, va.data_ptr(), vb.data_ptr(), w.data_ptr(), w.shape[0], n,
-                                            self.minClSize, labels.data_ptr(), k.ctypes.data), "flat labels")
+            if self.outlier_scores:
+                scores = torch.empty(n, dtype=torch.float64, device=dev)
+                noise = torch.empty(n, dtype=torch.float64, device=dev)
+                A.check(A.lib().hdb_flat_outlier_scores(c.h, va.data_ptr(), vb.data_ptr(), w.data_ptr(), w.shape[0], n,
+                                                        self.minClSize, scores.data_ptr(), noise.data_ptr(),
+                                                        labels.data_ptr(), k.ctypes.data), "flat labels + outlier scores")
+                out["outlier_scores"] = scores
+                out["noise_levels"] = noise
+            else:
+                A.check(A.lib().hdb_flat_labels(c.h, va.data_ptr(), vb.data_ptr(), w.data_ptr(), w.shape[0], n,
+                                                self.minClSize, labels.data_ptr(), k.ctypes.data), "flat labels")
             out["labels"] = labels
             out["n_clusters"] = int(k[0])
             self._mark("flat_labels")

@@ -95,6 +95,18 @@ def format_local_mst(va, vb, w, fake1=None, fake2=None, node=None) -> str:
     return buf.raw[: n.value].decode()
 
 
+def format_outlier_scores(scores, ids) -> str:
+    """The outlier-score file's text (HDBSCANStar.calculateOutlierScores :680-682 with its ","
+    delimiter): one line ``Double.toString(score) + "," + id + "\\n"`` per entry, in the order
+    given -- pass ``scores[p], p`` with ``p = outlier_ranking(scores, core)`` for the file the
+    reference writes."""
+    s = np.asarray(scores.detach().cpu().numpy() if hasattr(scores, "detach") else scores, dtype=np.float64)
+    i = np.asarray(ids.detach().cpu().numpy() if hasattr(ids, "detach") else ids, dtype=np.int64)
+    if s.shape != i.shape or s.ndim != 1:
+        raise ValueError("scores and ids must be one-dimensional and of the same length")
+    return "".join(f"{double_to_string(v)},{int(k)}\n" for v, k in zip(s, i))
+
+
 def parse_local_mst(text):
     """UnionFindReducer.java:22-45: the records of one text value as arrays
     ``(va, vb, w, fake1, fake2, node)``."""

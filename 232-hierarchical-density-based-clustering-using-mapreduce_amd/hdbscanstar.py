@@ -245,3 +245,40 @@ def flat_labels(va, vb, w, n: int, minClSize: int, ctx=None):
     A.check(A.lib().hdb_flat_labels(h, a.p, b.p, ww.p, ww.obj.shape[0], n, minClSize, A.ptr(labels), A.ptr(k)),
             "flat_labels")
     return labels, int(k[0])
+
+
+def outlier_scores(va, vb, w, n: int, minClSize: int, ctx=None, with_labels: bool = False):
+    """GLOSH outlier scores over the merged MST's hierarchy (HDBSCANStar.propagateTree :505-540,
+    calculateOutlierScores :653-686; the hierarchy and tie rules of flat_labels).  Returns
+    (scores[n], noise_level[n]), or (scores, noise_level, labels, K) with with_labels -- labels
+    and scores then come from the one hierarchy the call builds.
+
+    noise_level[x] = eps(x), the level at which x becomes noise; scores[x] = 0 when eps(x) == 0,
+    else 1 - eps_max(last(x)) / eps(x), with eps_max the lowest death level among the cluster x
+    leaves from and its descendants.  For the root cluster only its descendants count, and a root
+    that never splits into two valid children keeps Java's initial Double.MAX_VALUE
+    (Cluster.java:57,99-105): points leaving such a root get the reference's huge negative (or
+    -inf) scores, not a clamped value.  Device and host selection as in flat_labels."""
+    a, b, ww = A.Arr(va, np.int32), A.Arr(vb, np.int32), A.Arr(w, np.float64)
+    scores = A.new_like(a, (n,), np.float64)
+    noise = A.new_like(a, (n,), np.float64)
+    labels = A.new_like(a, (n,), np.int32) if with_labels else None
+    k = np.zeros(1, np.int64)
+    on_dev = a.device is not None and a.device.type == "cuda"
+    h = ctx.h if ctx is not None else (A.Context.get(a.device.index or 0).h if on_dev else None)
+    A.check(A.lib().hdb_flat_outlier_scores(h, a.p, b.p, ww.p, ww.obj.shape[0], n, minClSize, A.ptr(scores),
+                                            A.ptr(noise), A.ptr(labels), A.ptr(k) if with_labels else None),
+            "outlier_scores")
+    return (scores, noise, labels, int(k[0])) if with_labels else (scores, noise)
+
+
+def outlier_ranking(scores, core):
+    """The order calculateOutlierScores writes the points in: ascending (score, core distance,
+    id) under OutlierScore.compareTo's > / < comparisons (OutlierScore.java:36-50), so -0.0
+    ties 0.0.  Defined for non-NaN scores.  Returns the permutation (int64, host)."""
+    def host(x):
+        if A.is_torch(x):
+            x = x.detach().cpu().numpy()
+        return np.ascontiguousarray(x, dtype=np.float64) + 0.0  # -0.0 + 0.0 == +0.0: one key per value
+    s, c = host(scores), host(core)
+    return np.lexsort((np.arange(s.shape[0]), c, s)).astype(np.int64)

@@ -332,6 +332,29 @@ int hdb_local_mst_ids(hdb_ctx *ctx, const int32_t *ids, int64_t n, const int32_t
 int hdb_flat_labels(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, const double *w, int64_t ne, int64_t n,
                     int32_t min_cl_size, int32_t *labels, int64_t *n_clusters);
 
+/* GLOSH outlier scores over the same hierarchy (HDBSCANStar.propagateTree :505-540,
+ * calculateOutlierScores :653-686, Cluster.propagate :99-105), optionally with the flat labels
+ * of hdb_flat_labels from the one hierarchy the call builds.  Inputs, tie rules, pointer rules
+ * (device, host or mixed; ctx may be NULL when every pointer is host memory) and status codes
+ * are exactly those of hdb_flat_labels.
+ *   eps(x) (noise_level, pointNoiseLevels): the weight of the tie group whose removal leaves x
+ *     in a component of fewer than min_cl_size points; with n < min_cl_size every point leaves at
+ *     the heaviest edge's weight.  last(x) (pointLastClusters): the cluster x leaves from.
+ *   eps_max(C) (propagatedLowestChildDeathLevel): the lowest level at which C or any of its
+ *     descendant clusters loses its last points.  For the ROOT cluster only the descendants
+ *     count, and a root that never splits into two valid children keeps Java's initial
+ *     Double.MAX_VALUE: the points that leave such a root score 1 - DBL_MAX / eps(x), a huge
+ *     negative number or -inf, as the reference's arithmetic gives.
+ *   scores[x] = eps(x) == 0 ? 0.0 : 1.0 - eps_max(last(x)) / eps(x): one IEEE double division
+ *     and one subtraction, bit-identical on host and device.
+ * scores: n doubles, required.  noise_level (n doubles), labels (n ints, as hdb_flat_labels)
+ * and n_clusters may be NULL.  n == 0 is HDB_OK; n == 1 gives score 0 and noise level 0.
+ * Non-finite weights are out of scope.  Ranking and the output file are host formatting
+ * (ascending (score, core distance, id); "score,id" lines). */
+int hdb_flat_outlier_scores(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, const double *w, int64_t ne,
+                            int64_t n, int32_t min_cl_size, double *scores, double *noise_level, int32_t *labels,
+                            int64_t *n_clusters);
+
 /* -------------------------------------------------- record formats (§8(f) #3)
  * Host-only (no context, no device); see csrc/formats.cpp. */
 
