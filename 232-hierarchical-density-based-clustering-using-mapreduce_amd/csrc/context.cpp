@@ -236,7 +236,7 @@ int hdb_ctx_create(int device, hdb_ctx **out) {
         HIP_CHECK(hipGetDeviceProperties(&prop, device));
         c->num_cus = prop.multiProcessorCount;
         for (const char *k : {"prim_coop_plain_retries", "prim_coop_steps", "prim_coop_launches", "bubble_knn_replay_overflows",
-                              "boruvka_visits_sum", "boruvka_evals_sum", "boruvka_bound_ns_sum"})
+                              "boruvka_visits_sum", "boruvka_evals_sum", "boruvka_bound_ns_sum", "boruvka_inf_edges"})
             c->stats[k] = 0;
         if (const char *e = getenv("HDB_PRIM_COOP_SLOTS"))  // A/B knob
             c->prim_coop_slots = (atoi(e) == 6 && !hdb_prim_spec_built()) ? 4 : atoi(e);

@@ -64,6 +64,12 @@ void exact_leaf_device(hdb_ctx *ctx, const double *X, int64_t n, int d, int min_
                        double *core, int self_edges, int32_t *va, int32_t *vb, double *w);
 void boruvka_device(hdb_ctx *ctx, const double *X, int64_t n, int d, const double *core, int metric, int32_t *va,
                     int32_t *vb, double *w);
+// K2b's infinite-weight tail on host arrays (inf_edges.cpp): X, core in id order; (ea, eb)[m] the
+// finite edges K2b found.  Writes the +inf edges that join their trees under (w, s, lo, hi) and
+// returns their count; rows_left / first_left: rows outside the largest tree that only NaN
+// pairs reach (0 / -1 when the tree spans).
+int64_t inf_edges_host(const double *X, const double *core, int64_t n, int d, const int32_t *ea, const int32_t *eb,
+                       int64_t m, int32_t *oa, int32_t *ob, double *ow, int64_t *rows_left, int32_t *first_left);
 
 // K6 rank-order vertex labels: contracted labels reach nv + rank < 3m, stored as int32
 inline bool flat_relabel_fits(int64_t m) { return m >= 0 && 3 * m < (int64_t)INT32_MAX; }

@@ -2162,10 +2162,11 @@ static void boruvka_on_index(hdb_ctx *ctx, Spatial<D> &sp, int64_t n, char *extr
         for (auto e : round_ev) (void)hipEventDestroy(e);
         round_ev.clear();
     };
+    int stalled_round = -1;
     for (int round = 0; n > 1; round++) {
         if (round >= max_rounds || round >= PINNED_WORDS) {
             release_events();
-            HDB_THROW(HDB_EINVAL, "boruvka did not converge (non-finite distances?)");
+            HDB_THROW(HDB_EINVAL, "boruvka did not converge (internal error)");
         }
         // internal node tags -> EMPTY, then relabel (previous round's hook roots) + tags
         const int64_t n_inner = bvh.off[bvh.levels] - bvh.off[1];
@@ -2260,12 +2261,44 @@ static void boruvka_on_index(hdb_ctx *ctx, Spatial<D> &sp, int64_t n, char *extr
         HIP_CHECK(hipEventSynchronize(round_ev[round - 1]));
         const int64_t c = hcnt[round - 1];
         if (c >= n - 1) break;  // the tree was complete: round `round` was a no-op
-        if (round >= 2 && c == hcnt[round - 2]) {
-            release_events();
-            HDB_THROW(HDB_EINVAL, "boruvka made no progress (non-finite distances?)");
+        if (round >= 2 && c == hcnt[round - 2]) {  // no finite edge is left between two trees
+            stalled_round = round;
+            break;
         }
     }
     release_events();
+    if (stalled_round >= 0) {
+        // The kernels read w == +inf as "no edge" and drop NaN pairs, so what they found is the
+        // minimum spanning forest of the finite edges; the +inf edges that join its trees come
+        // from the host (inf_edges.cpp), and trees that only NaN pairs reach are an error.
+        HIP_CHECK(hipStreamSynchronize(st));
+        const int64_t m = hcnt[stalled_round];
+        std::vector<Rec<D>> hr(per);
+        std::vector<int32_t> ha(per), hb(per);
+        HIP_CHECK(hipMemcpyAsync(hr.data(), recs, sizeof(Rec<D>) * per, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(ha.data(), ea, 4 * (size_t)m, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(hb.data(), eb, 4 * (size_t)m, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        std::vector<double> hx(per * D), hc(per), hw(per);
+        for (int64_t i = 0; i < n; i++) {
+            const Rec<D> &r = hr[i];
+            for (int c = 0; c < D; c++) hx[(size_t)r.id * D + c] = r.x[c];
+            hc[r.id] = r.core;
+        }
+        int64_t left = 0;
+        int32_t first = -1;
+        const int64_t added = inf_edges_host(hx.data(), hc.data(), n, D, ha.data(), hb.data(), m, ha.data() + m,
+                                             hb.data() + m, hw.data() + m, &left, &first);
+        ctx->stats["boruvka_inf_edges"] += added;
+        if (m + added != n - 1)
+            HDB_THROW(HDB_EINVAL, "boruvka: non-finite input: " + std::to_string(left) +
+                                      " row(s) have only NaN distances to the other rows (first: row " +
+                                      std::to_string(first) + ")");
+        HIP_CHECK(hipMemcpyAsync(ea + m, ha.data() + m, 4 * (size_t)added, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(eb + m, hb.data() + m, 4 * (size_t)added, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(ew + m, hw.data() + m, 8 * (size_t)added, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipStreamSynchronize(st));  // the host vectors die with this block
+    }
     if (evals) {
         ctx->stats["boruvka_evals"] = tot_evals;
         ctx->stats["last_evals"] = tot_evals;

@@ -184,7 +184,25 @@ int hdb_leaf_msts(hdb_ctx *ctx, const double *X, const int64_t *offsets, int32_t
 /* Exact minimum spanning tree of the mutual-reachability graph for large n (Boruvka,
  * K2b).  Any MST: the sorted weight sequence equals the reference Prim's exactly; the
  * topology can differ only among equal-weight edges (ties broken by (w, min id, max id)).
- * Outputs n-1 edges (va < vb, by the library's order), then n self edges if self_edges. */
+ * Outputs n-1 edges (va < vb, by the library's order), then n self edges if self_edges.
+ *
+ * Exactly: the unique MST under the strict total edge order (w, s, min id, max id), with
+ * w = max(sqrt(s), core_p, core_q) (HDBSCANStar.java:162-168) and s the squared distance summed
+ * in dimension order.  Non-finite and signed-zero input (the same for hdb_exact_mst):
+ *  - A pair whose mutual-reachability distance is NaN (a NaN coordinate; inf - inf in one
+ *    coordinate) is not an edge.
+ *  - A row with an infinite coordinate, a squared distance that overflows or an infinite core
+ *    gives edges of weight +inf.  They are edges like any other and fall under the same tie
+ *    rule: among +inf weights the smaller s wins, then the smaller ids.  (The device rounds
+ *    find the finite edges; the +inf edges that join what is left are chosen on the host, stat
+ *    "boruvka_inf_edges".)
+ *  - Input whose non-NaN pairs do not connect all rows (e.g. any row with a NaN coordinate) is
+ *    HDB_EINVAL with a message that names "non-finite input", the number of unreachable rows
+ *    and the first of them.  No output is defined then; the context stays usable.
+ *  - A NaN core never raises a weight (the reference's '>' comparisons), and neither does a
+ *    -0.0 core: weights compare as numbers, so -0.0 acts as +0.0.  A tree edge's weight is
+ *    never -0.0 (it starts from sqrt(s) >= +0.0 and only a strictly larger core replaces it);
+ *    a self edge's weight is the core as passed, so a -0.0 core comes back as -0.0 there. */
 int hdb_mst_boruvka(hdb_ctx *ctx, const double *X, int64_t n, int32_t d, const double *core, int32_t metric,
                     int32_t self_edges, int32_t *va, int32_t *vb, double *w);
 
@@ -192,7 +210,9 @@ int hdb_mst_boruvka(hdb_ctx *ctx, const double *X, int64_t n, int32_t d, const d
  * HDBSCANStar.calculateCoreDistances then constructMST): core distances (semantics as
  * hdb_core_distances, bit-identical) and the exact mutual-reachability MST of
  * hdb_mst_boruvka (same weights and edge order), sharing one spatial index; the k-NN lists
- * seed every Boruvka round.  core_out nullable.  Local vertex ids 0..n-1. */
+ * seed every Boruvka round.  core_out nullable.  Local vertex ids 0..n-1.
+ * NaN pairs, +inf weights and rows that no non-NaN pair reaches (HDB_EINVAL, "non-finite
+ * input") are handled exactly as documented at hdb_mst_boruvka; core_out is then undefined. */
 #define HDB_EDGES_SELF 1   /* append the n self edges (HDBSCANStar.java:196-203)                  */
 #define HDB_EDGES_MERGED 2 /* return the edges in the reducers' merge order instead: exactly what
                               hdb_sort_edges_desc returns for the plain list (UnionFindReducer.java:

@@ -57,7 +57,8 @@ def kruskal_mst(X, core):
     max(sqrt(s), core_lo, core_hi), s the squared distance summed in dimension order
     (EuclideanDistance.java:31-33, every operation rounded once), lo < hi the point indices.
     A total order makes the MST unique, so plain Kruskal over all pairs pins every edge.
-    Returns (lo, hi, w) of the n - 1 edges in key order.
+    A pair whose weight is NaN is not an edge; if the rest does not span, ValueError names the
+    rows outside the largest component.  Returns (lo, hi, w) of the n - 1 edges in key order.
 
     All pairs are formed at once (vectorised); the sorted prefix is consumed in chunks, and
     after each chunk the pairs inside one component are dropped, so the Python union-find loop
@@ -66,12 +67,14 @@ def kruskal_mst(X, core):
     core = np.ascontiguousarray(core, np.float64)
     n, d = X.shape
     i, j = _pairs(n)
-    t = X[i, 0] - X[j, 0]
-    s = t * t
-    for k in range(1, d):
-        t = X[i, k] - X[j, k]
-        s = s + t * t
-    w = np.maximum(np.sqrt(s), np.maximum(core[i], core[j]))
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+        t = X[i, 0] - X[j, 0]
+        s = t * t
+        for k in range(1, d):
+            t = X[i, k] - X[j, k]
+            s = s + t * t
+        # weights compare as numbers: + 0.0 turns a -0.0 (from -0.0 cores) into the +0.0 it ties with
+        w = np.maximum(np.sqrt(s), np.maximum(core[i], core[j])) + 0.0
     parent = list(range(n))
 
     def find(x):
@@ -81,9 +84,12 @@ def kruskal_mst(X, core):
         return x
 
     out = []
-    idx = np.arange(w.shape[0])
+    idx = np.flatnonzero(~np.isnan(w))  # a pair whose weight is NaN is not an edge
     while len(out) < n - 1:
-        assert idx.shape[0] > 0, "the pairs ran out before the tree spanned"
+        if idx.shape[0] == 0:
+            root = np.fromiter((find(x) for x in range(n)), np.int64, n)
+            big = np.bincount(root).argmax()
+            raise ValueError("the non-NaN pairs do not span: isolated rows %s" % np.flatnonzero(root != big).tolist())
         take = min(idx.shape[0], 8 * n)
         wi = w[idx]
         sel = wi <= np.partition(wi, take - 1)[take - 1]  # whole tie groups: the rest is strictly heavier
@@ -94,6 +100,8 @@ def kruskal_mst(X, core):
             if ra != rb:
                 parent[rb] = ra
                 out.append(e)
+                if len(out) == n - 1:
+                    break
         root = np.fromiter((find(x) for x in range(n)), np.int64, n)
         idx = idx[root[i[idx]] != root[j[idx]]]
     out = np.asarray(out, np.int64)

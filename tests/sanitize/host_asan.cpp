@@ -1,9 +1,11 @@
 // ASan/UBSan driver for the product's host C++: csrc/flat.cpp (global flat
 // labels), csrc/formats.cpp (record formats), csrc/local_model.cpp (bubble core epilogue,
-// UndirectedGraph quicksort, cluster tree, FOSC + noise reassignment).  Built by
+// UndirectedGraph quicksort, cluster tree, FOSC + noise reassignment), csrc/inf_edges.cpp (the
+// exact leaf's infinite-weight tail, against an all-pairs Kruskal).  Built by
 // tests/sanitize/Makefile (hipcc --cuda-host-only -fsanitize=address,undefined) and run by
 // tests/test_sanitizers.py on tie-heavy seeded inputs and malformed records.  The library's
 // error setter lives in context.cpp (HIP runtime); a host stub stands in for it here.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -154,6 +156,85 @@ static void local_model() {
     }
 }
 
+// csrc/inf_edges.cpp against Kruskal over all pairs under (w, s, lo, hi): small inputs with
+// overflowing, infinite and NaN rows; the finite edges of Kruskal's tree go in (what K2b's
+// device rounds find), its +inf edges must come out, and rows that only NaN pairs reach are counted
+static bool inf_tail() {
+    struct E {
+        double w, s;
+        int32_t lo, hi;
+    };
+    for (int t = 0; t < 60; t++) {
+        const int n = 2 + irand(150), d = 1 + irand(4);
+        std::vector<double> X((size_t)n * d), core(n);
+        for (auto &x : X) x = std::round(urand() * 8.0);
+        for (int i = 0; i < n; i++) core[i] = irand(4) == 0 ? -0.0 : irand(3) * 0.5;
+        const int bad = t % 6 == 0 ? 0 : 1 + irand(1 + n / 4);
+        for (int k = 0; k < bad; k++) {
+            const int r = irand(n), c = irand(d);
+            switch (t % 5) {
+            case 0: X[(size_t)r * d + c] = INFINITY; break;
+            case 1: X[(size_t)r * d + c] = (irand(2) ? 1e200 : -1.7e308) * (1 + irand(3)); break;
+            case 2: core[r] = INFINITY; break;
+            case 3: X[(size_t)r * d + c] = irand(2) ? NAN : -INFINITY; break;
+            default: for (int cc = 0; cc < d; cc++) X[(size_t)r * d + cc] = 1e160 * (irand(5) - 2); break;
+            }
+        }
+        std::vector<E> es;
+        for (int p = 0; p < n; p++)
+            for (int q = p + 1; q < n; q++) {
+                double u = X[(size_t)p * d] - X[(size_t)q * d], s = u * u;
+                for (int c = 1; c < d; c++) {
+                    u = X[(size_t)p * d + c] - X[(size_t)q * d + c];
+                    s = s + u * u;
+                }
+                double w = std::sqrt(s);
+                if (core[p] > w) w = core[p];
+                if (core[q] > w) w = core[q];
+                if (w == w) es.push_back(E{w, s, p, q});
+            }
+        std::sort(es.begin(), es.end(), [](const E &a, const E &b) {
+            if (a.w != b.w) return a.w < b.w;
+            if (a.s != b.s) return a.s < b.s;
+            return a.lo != b.lo ? a.lo < b.lo : a.hi < b.hi;
+        });
+        std::vector<int32_t> par(n), ea, eb, xa, xb, cnt(n, 0);
+        for (int i = 0; i < n; i++) par[i] = i;
+        auto find = [&](int32_t x) {
+            while (par[x] != x) x = par[x] = par[par[x]];
+            return x;
+        };
+        for (const E &e : es) {
+            const int32_t a = find(e.lo), b = find(e.hi);
+            if (a == b) continue;
+            par[b] = a;
+            (e.w < INFINITY ? ea : xa).push_back(e.lo);
+            (e.w < INFINITY ? eb : xb).push_back(e.hi);
+        }
+        int32_t biggest = 0;
+        for (int i = 0; i < n; i++) biggest = std::max(biggest, ++cnt[find(i)]);
+        std::vector<int32_t> oa(n), ob(n);
+        std::vector<double> ow(n);
+        int64_t left = -1;
+        int32_t first = -2;
+        const int64_t added = hdb::inf_edges_host(X.data(), core.data(), n, d, ea.data(), eb.data(), (int64_t)ea.size(),
+                                                  oa.data(), ob.data(), ow.data(), &left, &first);
+        std::vector<std::pair<int32_t, int32_t>> got, want;
+        for (int64_t i = 0; i < added; i++) got.emplace_back(oa[i], ob[i]);
+        for (size_t i = 0; i < xa.size(); i++) want.emplace_back(xa[i], xb[i]);
+        std::sort(got.begin(), got.end());
+        std::sort(want.begin(), want.end());
+        bool ok = got == want && left == n - biggest && (left == 0) == (first == -1);
+        for (int64_t i = 0; i < added; i++) ok = ok && ow[i] == INFINITY;
+        if (!ok) {
+            printf("inf_edges_host differs from Kruskal: trial %d n %d d %d added %lld want %zu left %lld\n", t, n, d,
+                   (long long)added, want.size(), (long long)left);
+            return false;
+        }
+    }
+    return true;
+}
+
 int main() {
     // K6 relabel limit (flat.hip): contracted labels nv + rank < 3m must fit int32
     if (!hdb::flat_relabel_fits(715827882) || hdb::flat_relabel_fits(715827883) || !hdb::flat_relabel_fits(0)) {
@@ -163,6 +244,7 @@ int main() {
     flat();
     formats();
     local_model();
+    if (!inf_tail()) return 1;
     printf("host asan ok\n");
     return 0;
 }
