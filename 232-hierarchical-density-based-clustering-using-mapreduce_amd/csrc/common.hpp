@@ -91,13 +91,12 @@ struct hdb_ctx {
     bool bubble_fold_dim = true;   // K4: one lane per (bubble, dimension) fold (0: one lane per bubble, A/B)
     bool bubble_knn_split = true;  // K5: candidate range in chunks + merge (one thread per bubble is 256 waves at 16k)
     bool prim_coop_xcd = true;     // plain attempt: working blocks on one XCD exchange through its L2 (checked at run time)
-    int prim_coop_xcd_max_wg = 32;  // ... for Prims of at most this many workgroups (one XCD: 32 CUs)
+                                   // (for Prims of at most PRIM_XCD_MAX_WG workgroups, prim.hip)
     int prim_coop_bs = 1024;  // cooperative Prim (slots 4/5) workgroup size; 0: the smallest of 128..1024 that keeps
-                              // the Prim within prim_coop_xcd_max_wg workgroups (more CUs share a step's relaxation)
+                              // the Prim within PRIM_XCD_MAX_WG workgroups (more CUs share a step's relaxation)
     int prim_coop_plain_spin_log2 = 20;  // plain attempt: polls per exchange before it reports non-co-residency
     int prim_coop_slots = 4;  // cooperative Prim exchange, rows in registers (d <= 16): 1 release/acquire slots, 2 granules,
                               // 3 drained sc1 slots, 4 DPP folds + key granules (default), 5 key+row granule sweep
-    bool merge_runs = false;   // merge sort: radix-sort only what follows a non-decreasing prefix, then merge (slower as built: sync + binary searches)
     int flat_link_variant = 1;  // K6 dc_link A/B: 0 direct guarded atomics, 1 LDS-combined multi-batch
     int flat_root_variant = 3;  // K6 dc_root A/B: 0 LDS table (256 threads), 1 (1024), 2 direct atomics, 3-5 multi-batch
     bool flat_relabel = true;  // K6: divide-and-conquer vertex labels in rank order (locality; false: point ids)

@@ -4,6 +4,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <cerrno>
 #include <cstdlib>
 
 #include "common.hpp"
@@ -215,6 +216,34 @@ void Stager::finish() {
 
 using namespace hdb;
 
+// "name=value,name=value" through hdb_ctx_set_option; the first pair that is malformed or
+// rejected ends it with that status and names the pair in last_error()
+static int apply_opts(hdb_ctx *c, const char *opts) {
+    const std::string s(opts);
+    for (size_t a = 0; a < s.size();) {
+        const size_t b = std::min(s.find(',', a), s.size());
+        const std::string pair = s.substr(a, b - a);
+        a = b + 1;
+        if (pair.empty()) continue;
+        const size_t eq = pair.find('=');
+        char *end = nullptr;
+        errno = 0;
+        const long long v = eq == std::string::npos ? 0 : strtoll(pair.c_str() + eq + 1, &end, 10);
+        if (eq == std::string::npos || eq == 0 || end == pair.c_str() + eq + 1 || *end != '\0' || errno == ERANGE) {
+            set_error("malformed pair '" + pair + "' (name=integer)");
+            return HDB_EINVAL;
+        }
+        set_error("");
+        const int rc = hdb_ctx_set_option(c, pair.substr(0, eq).c_str(), (int64_t)v);
+        if (rc != HDB_OK) {
+            const std::string why = last_error();
+            set_error("'" + pair + "' rejected" + (why.empty() ? std::string(" (value out of range)") : ": " + why));
+            return rc;
+        }
+    }
+    return HDB_OK;
+}
+
 extern "C" {
 
 const char *hdb_last_error(void) { return hdb::last_error(); }
@@ -238,29 +267,18 @@ int hdb_ctx_create(int device, hdb_ctx **out) {
         for (const char *k : {"prim_coop_plain_retries", "prim_coop_steps", "prim_coop_launches", "bubble_knn_replay_overflows",
                               "boruvka_visits_sum", "boruvka_evals_sum", "boruvka_bound_ns_sum", "boruvka_inf_edges"})
             c->stats[k] = 0;
-        if (const char *e = getenv("HDB_PRIM_COOP_SLOTS"))  // A/B knob
-            c->prim_coop_slots = (atoi(e) == 6 && !hdb_prim_spec_built()) ? 4 : atoi(e);
         // per-kernel HIP-event timing from birth (contexts created on worker threads, bench.py)
         if (const char *e = getenv("HDB_KERNEL_TIMING")) c->timing = atoi(e) != 0;
-        if (const char *e = getenv("HDB_FLAT_BLOCK_LOG")) c->flat_block_log = atoi(e);  // A/B knob
-        if (const char *e = getenv("HDB_PRIM_XCD")) c->prim_coop_xcd = atoi(e) != 0;       // A/B knob
-        if (const char *e = getenv("HDB_BUBBLE_SPLIT")) c->bubble_knn_split = atoi(e) != 0;  // A/B knob
-        if (const char *e = getenv("HDB_PRIM_XCD_MAX_WG")) c->prim_coop_xcd_max_wg = atoi(e);  // A/B knob
-        if (const char *e = getenv("HDB_PRIM_COOP_BS")) c->prim_coop_bs = atoi(e);             // A/B knob
-        if (const char *e = getenv("HDB_FLAT_LINK")) c->flat_link_variant = atoi(e);      // A/B knob
-        if (const char *e = getenv("HDB_FLAT_ROOT")) c->flat_root_variant = atoi(e);      // A/B knob
-        if (const char *e = getenv("HDB_MERGE_RUNS")) c->merge_runs = atoi(e) != 0;      // A/B knob
-        if (const char *e = getenv("HDB_SSORT")) c->ssort = atoi(e) != 0;                // A/B knob
-        if (const char *e = getenv("HDB_FLAT_RELABEL")) c->flat_relabel = atoi(e) != 0;  // A/B knob
-        if (const char *e = getenv("HDB_FLAT_DEEP")) c->flat_deep_depth = atoi(e);          // A/B knob
-        if (const char *e = getenv("HDB_FLAT_MID")) c->flat_mid_log = atoi(e);              // A/B knob
-        if (const char *e = getenv("HDB_FLAT_DEEP_ROOT")) c->flat_deep_root = atoi(e);      // A/B knob
-        if (const char *e = getenv("HDB_FLAT_DEEP_LINK")) c->flat_deep_link = atoi(e);      // A/B knob
-        if (const char *e = getenv("HDB_BOR_EARLY_PTS")) c->boruvka_early_pts = atoi(e);    // A/B knob
-        if (const char *e = getenv("HDB_BOR_ADJ")) c->boruvka_adj_seed = atoi(e) != 0;      // A/B knob
-        if (const char *e = getenv("HDB_K1T_XCD")) c->k1t_xcd_chunks = atoi(e);             // A/B knob
-        if (const char *e = getenv("HDB_BOR_XCD")) c->bor_xcd_chunks = atoi(e);             // A/B knob
-        if (const char *e = getenv("HDB_BOR_EARLY_ROUNDS")) c->boruvka_early_rounds = atoi(e);  // A/B knob
+        // A/B runs of unmodified programs: HDB_OPTS="name=value,name=value", every pair applied
+        // with hdb_ctx_set_option (its range checks included); a pair it rejects fails the create
+        if (const char *e = getenv("HDB_OPTS")) {
+            const int rc = apply_opts(c, e);
+            if (rc != HDB_OK) {
+                const std::string msg = std::string("HDB_OPTS: ") + last_error();
+                hdb_ctx_destroy(c);
+                HDB_THROW(rc, msg);
+            }
+        }
         *out = c;
         return HDB_OK;
     } catch (const Error &e) {

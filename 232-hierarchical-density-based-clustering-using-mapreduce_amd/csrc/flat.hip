@@ -1976,12 +1976,10 @@ static void flat_device_impl(hdb_ctx *ctx, const int32_t *va, const int32_t *vb,
     for (int64_t span = 5; span < m; span *= 5) rounds++;
     rounds = std::min(rounds, 64);
     // pointer-jumping grids (grid-stride): most launches only see the previous launch's zero
-    // flag and return, so a grid of at most HDB_JUMP_WG workgroups (0: one element per thread;
-    // 256: jump kernels 303 -> 265 us per C2 partition, profiles/r06/jump/)
-#ifndef HDB_JUMP_WG
-#define HDB_JUMP_WG 256
-#endif
-    const unsigned jump_wg = (unsigned)(HDB_JUMP_WG > 0 ? std::min<int64_t>(g / 4 + 1, HDB_JUMP_WG) : g / 4 + 1);
+    // flag and return, so a grid of at most JUMP_WG workgroups (against one element per thread:
+    // jump kernels 303 -> 265 us per C2 partition, profiles/r06/jump/)
+    constexpr int JUMP_WG = 256;
+    const unsigned jump_wg = (unsigned)std::min<int64_t>(g / 4 + 1, JUMP_WG);
     auto jump_all = [&](int32_t *up, int nr) {  // roots of an upward forest, in place
         HIP_CHECK(hipMemsetAsync(jflags, 0, sizeof(int) * 64, st));
         for (int k = 0; k < nr; k++)

@@ -360,14 +360,8 @@ template <int D, int K, int Q, bool EXCL, bool IDX>
 void launch_knn_sq(hdb_ctx *ctx, const double *Xp, int64_t n, double *out_v, int32_t *out_i) {
     constexpr int DP = (D + 1) & ~1;
     constexpr int DF = D <= 4 ? 4 : (D <= 8 ? 8 : 16);
-#ifndef HDB_KNN_U
-#define HDB_KNN_U 4
-#endif
-    constexpr int U = (D <= 4) ? HDB_KNN_U : 2;
-#ifndef HDB_KNN_US
-#define HDB_KNN_US 8
-#endif
-    constexpr int US = (D <= 4) ? HDB_KNN_US : (D <= 8 ? 4 : 2);  // screen kernel group
+    constexpr int U = (D <= 4) ? 4 : 2;
+    constexpr int US = (D <= 4) ? 8 : (D <= 8 ? 4 : 2);  // screen kernel group
     KnnPlan p = plan_knn(ctx, n, Q);
     dim3 grid(p.tiles, p.S);
     const bool f32 = g_screen.on;
@@ -394,13 +388,10 @@ void launch_knn_sq(hdb_ctx *ctx, const double *Xp, int64_t n, double *out_v, int
     HIP_CHECK(hipGetLastError());
 }
 
-#ifndef HDB_KNN_Q
-#define HDB_KNN_Q 4
-#endif
 template <int D, int K, bool EXCL, bool IDX>
 void dispatch_q(hdb_ctx *ctx, const double *Xp, int64_t n, double *ov, int32_t *oi) {
     // queries per lane: keep D*Q + K*Q doubles well inside the register budget
-    constexpr int Q = (D * 2 + K * (IDX ? 3 : 2) <= 24) ? HDB_KNN_Q : ((D + K) <= 24 ? 2 : 1);
+    constexpr int Q = (D * 2 + K * (IDX ? 3 : 2) <= 24) ? 4 : ((D + K) <= 24 ? 2 : 1);
     launch_knn_sq<D, K, Q, EXCL, IDX>(ctx, Xp, n, ov, oi);
 }
 

@@ -357,29 +357,19 @@ struct LogEnt {
 };
 constexpr int S_CST = 192;  // per 32-candidate block: hc[32], cn[32] (float), c2[32], cn[32] (double)
 
-#ifndef HDB_K1S_WAVES
 // waves per workgroup.  The block loop's one barrier per 32-candidate block makes every wave
 // wait for the slowest one's hit path; two 4-wave workgroups per CU (128 queries each) wait
 // on fewer waves and independently: screen 33.0 -> 31.1 ms at C4 (r05; round 3 measured 8
 // against 4 waves x 2 query tiles: 51.9 vs 56.0 ms)
-#define HDB_K1S_WAVES 4
-#endif
-#ifndef HDB_K1S_QT
-#define HDB_K1S_QT 1  // query tiles per wave at DP <= 128 (64 fragment VGPRs: 4 waves per SIMD)
-#endif
-constexpr int NW = HDB_K1S_WAVES;
-#ifndef HDB_K1S_XCD
-#define HDB_K1S_XCD 1  // contiguous query-group ranges per XCD (A/B at C4: screen 51.8 -> 50.7 ms)
-#endif
-#ifndef HDB_K1S_REGTOP
-// 1: each lane keeps the running top-KC upper bounds of its (query, half-wave) pair in
-// registers and logs into its own half of the query's log, so the two half-waves of a wave
-// take their hits at the same time and an insertion is a register network instead of a
-// dependent LDS shift chain (KC <= 15).  The query's threshold is the KC-th smallest bound of
+constexpr int NW = 4;
+constexpr int K1S_QT = 1;  // query tiles per wave at DP <= 128 (64 fragment VGPRs: 4 waves per SIMD)
+// Register top lists (KC <= 15): each lane keeps the running top-KC upper bounds of its (query,
+// half-wave) pair in registers and logs into its own half of the query's log, so the two
+// half-waves of a wave take their hits at the same time and an insertion is a register network
+// instead of a dependent LDS shift chain.  The query's threshold is the KC-th smallest bound of
 // the union of its two halves' lists (the halves see disjoint candidate rows, so the union
-// holds bounds of distinct candidates: >= the KC-th exact value), refreshed per hit step
-#define HDB_K1S_REGTOP 1
-#endif
+// holds bounds of distinct candidates: >= the KC-th exact value), refreshed per hit step.
+// KC = 31 keeps one LDS list per query.
 #ifndef HDB_K1S_PROF
 #define HDB_K1S_PROF 0  // diagnostic build: per-wave cycle split of the screen loop (stats k1s_prof_*)
 #endif
@@ -387,25 +377,22 @@ constexpr int NW = HDB_K1S_WAVES;
 // 8-entry LDS buffer per (query, half) flushed 64 bytes at a time, and entry pairs held in
 // registers and stored as 16 bytes: HBM writes 6.54 -> 3.04 / 5.09 GB per launch at C4, but
 // the screen took 36.9 -> 38.2 / 39.0 ms, the longer hit path costing more than the traffic)
-#ifndef HDB_K1F_XCD
-#define HDB_K1F_XCD 1  // K1m re-check: contiguous 16-query workgroup ranges per XCD (shared candidate rows in one L2)
-#endif
-#define K1S_XCD HDB_K1S_XCD
 // Workgroups are dealt round-robin over the 8 XCDs (block b runs on XCD b mod 8); this maps
-// them so XCD x takes one contiguous range of logical blocks (a bijection on [0, G)).
+// them so XCD x takes one contiguous range of logical blocks (a bijection on [0, G)).  The
+// screen uses it for its query-group ranges (A/B at C4: screen 51.8 -> 50.7 ms) and the K1m
+// re-check for its 16-query workgroups (shared candidate rows in one L2).
 __device__ __forceinline__ int64_t xcd_contig(int64_t b, int64_t G) {
     const int64_t q = G >> 3, r = G & 7, x = b & 7, k = b >> 3;
     return x < r ? x * (q + 1) + k : r * (q + 1) + (x - r) * q + k;
 }
-#ifndef HDB_K1S_WPE
-#define HDB_K1S_WPE (HDB_K1S_QT == 1 ? (HDB_K1S_REGTOP ? 2 : 4) : 2)  // REGTOP: one 8-wave workgroup per CU
-                                                                      // either way; 2 leaves 192 VGPRs (A/B: 37.5 -> 36.9 ms)
-#endif
-constexpr int K1S_WPE = HDB_K1S_WPE;  // waves per SIMD (A/B at C4: 4 = two workgroups per CU, 51.7 ms, despite
-                                      // spilling some fragments; 3 = 168 VGPRs without spills, one workgroup, 57.0 ms)
+// waves per SIMD the screen is compiled for: with the register lists one 8-wave workgroup per
+// CU either way, and 2 leaves 192 VGPRs (A/B: 37.5 -> 36.9 ms; before the register lists, at
+// C4: 4 = two workgroups per CU, 51.7 ms, despite spilling some fragments; 3 = 168 VGPRs
+// without spills, one workgroup, 57.0 ms)
+constexpr int K1S_WPE = 2;
 template <int DP>
 struct ScreenCfg {
-    static constexpr int QT = DP <= 128 ? HDB_K1S_QT : 1;  // query tiles per wave (VGPR-resident fragments)
+    static constexpr int QT = DP <= 128 ? K1S_QT : 1;  // query tiles per wave (VGPR-resident fragments)
     static constexpr int SQ = NW * 32 * QT;       // queries per workgroup
     static constexpr int CH = DP / 8;             // 16-B chunks per bf16 row
     static constexpr int BUF = 2 * 32 * DP;       // bf16 elements per staged block (hi rows, lo rows)
@@ -827,7 +814,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(K1S_WPE
         if constexpr (decltype(B)::value == 0) return cst0_s;
         else return cst1_s;
     };
-    constexpr bool REG = HDB_K1S_REGTOP && KC <= 15;  // register lists (see HDB_K1S_REGTOP)
+    constexpr bool REG = KC <= 15;  // register top lists (see above)
     static_assert(!REG || QT == 1, "register top lists hold one query per lane");
     constexpr int LH = S_LOGCAP / 2;  // REG: entries per half-query log
     constexpr int KR = REG ? KC : 1, KT = KR - 1;  // register list length, its last slot
@@ -851,14 +838,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(K1S_WPE
     const uint64_t p_t0 = __builtin_readcyclecounter();
     uint64_t p_wait = 0, p_mfma = 0, p_hit = 0, p_hitsteps = 0, p_hits = 0, p_setup = 0;
 #endif
-#if K1S_XCD
     // query groups of one k-means cluster are consecutive and visit the same candidate
     // superblocks: give each XCD (workgroups are dealt round-robin over the 8) a contiguous
     // range of groups, so those candidates are fetched into one L2 instead of eight
     const int64_t gid = xcd_contig(blockIdx.x, gridDim.x);
-#else
-    const int64_t gid = blockIdx.x;
-#endif
     const int64_t qbase = gid * SQ;
     {
         // a group of padding rows only (uniform: every thread reads the same rows)
@@ -1295,26 +1278,16 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(K1S_WPE
     }
 }
 
-#ifndef HDB_K1F_LAYOUT
-#define HDB_K1F_LAYOUT 1  // K1m re-check reads an FP64 copy of the rows in layout order (written by split_rows_kernel)
-#endif
-#ifndef HDB_K1F_WPE
-#define HDB_K1F_WPE 1  // K1m re-check: waves per SIMD the kernel is compiled for (1: no cap)
-#endif
-#ifndef HDB_K1F_DIST
-#define HDB_K1F_DIST 1  // K1m re-check: the group's running top-KC distributed over its 16 lanes
-#endif
-#ifndef HDB_K1F_LAY_UNROLL
-#define HDB_K1F_LAY_UNROLL 1
-#endif
-#ifndef HDB_K1F_U
-#define HDB_K1F_U 16  // doubles per prefetched chunk (r04 C4 A/B, layout rows: 8.87 ms at 8, 8.15 at 16; caller-order rows: 15.2 at 8, 15.6 at 16, 17.1 at 32)
-#endif
+// K1m re-check.  It reads an FP64 copy of the rows in layout order (written by
+// split_rows_kernel; the caller-order rows are the fallback when that copy cannot be
+// allocated) and keeps the group's running top-KC distributed over its 16 lanes (KC <= 16).
+constexpr int K1F_WPE = 1;  // waves per SIMD the kernel is compiled for (1: no cap)
+constexpr int K1F_U = 16;   // doubles per prefetched chunk (r04 C4 A/B, layout rows: 8.87 ms at 8, 8.15 at 16; caller-order rows: 15.2 at 8, 15.6 at 16, 17.1 at 32)
 // exact squared distance in the reference's order with the query row in LDS and the candidate
 // row (caller order, runtime length d) streamed in U-double chunks, the next chunk in flight
 // while the current one is summed
 __device__ __forceinline__ double exact_sq_pf(const double *a_lds, const double *__restrict__ b, int d) {
-    constexpr int U = HDB_K1F_U;  // doubles per prefetched chunk
+    constexpr int U = K1F_U;
     double nb[U];
 #pragma unroll
     for (int u = 0; u < U; u++) nb[u] = b[u < d ? u : d - 1];
@@ -1338,13 +1311,13 @@ __device__ __forceinline__ double exact_sq_pf(const double *a_lds, const double 
 // addresses): the padded terms are (0 - 0)^2 = +0, and s + 0 == s, so the value is bit-equal
 template <int DP>
 __device__ __forceinline__ double exact_sq_lay(const double *a_lds, const double *__restrict__ b) {
-    constexpr int U = HDB_K1F_U;
+    constexpr int U = K1F_U;
     static_assert(DP % U == 0, "chunk must divide the padded row");
     double nb[U];
 #pragma unroll
     for (int u = 0; u < U; u++) nb[u] = b[u];
     double sx = 0.0;
-#pragma unroll HDB_K1F_LAY_UNROLL
+#pragma unroll 1
     for (int j0 = 0; j0 < DP; j0 += U) {
         double cb[U];
 #pragma unroll
@@ -1370,14 +1343,14 @@ __device__ __forceinline__ double exact_sq_lay(const double *a_lds, const double
 // Query rows in dynamic LDS (16 x DP, or 16 x d).
 constexpr int K1F_CH = 256;  // compacted survivors per group and pass
 template <int KC, int DP, bool LAY>
-__global__ __launch_bounds__(256, HDB_K1F_WPE) void knn_mfma_final16_kernel(const double *__restrict__ X, int64_t n, int d,
+__global__ __launch_bounds__(256, K1F_WPE) void knn_mfma_final16_kernel(const double *__restrict__ X, int64_t n, int d,
                                                                const LogEnt *__restrict__ logs,
                                                                const int *__restrict__ log_cnt,
                                                                const float *__restrict__ thr,
                                                                const int *__restrict__ perm,
                                                                double *__restrict__ lists,
                                                                const double *__restrict__ Xlay) {
-    constexpr bool REG = HDB_K1S_REGTOP && KC <= 15;
+    constexpr bool REG = KC <= 15;  // the screen's register top lists: two half-query logs
     constexpr int NH = REG ? 2 : 1, LH = S_LOGCAP / NH;
     extern __shared__ __attribute__((aligned(16))) double k1f_dyn[];
     __shared__ int cl_s[16][K1F_CH];
@@ -1385,7 +1358,7 @@ __global__ __launch_bounds__(256, HDB_K1F_WPE) void knn_mfma_final16_kernel(cons
     const int g = (threadIdx.x >> 6) * 4 + sub;  // query slot in the workgroup
     // consecutive workgroups (one k-means cluster) share candidate rows: with XCD-contiguous
     // ranges those rows are fetched into one L2 instead of eight
-    const int64_t q = (HDB_K1F_XCD ? xcd_contig(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x) * 16 + g;
+    const int64_t q = xcd_contig(blockIdx.x, gridDim.x) * 16 + g;
     const bool act = q < n && perm[q] >= 0;  // n: layout rows here (uniform per 16 lanes)
     const int rs = LAY ? DP : d;  // query row length in LDS
     double *qr = k1f_dyn + (size_t)g * rs;
@@ -1400,7 +1373,7 @@ __global__ __launch_bounds__(256, HDB_K1F_WPE) void knn_mfma_final16_kernel(cons
     // DIST: the group's running KC smallest live one per lane (lane sl: the sl-th), merged with
     // each batch of <= 64 exact values by KC rounds of a 16-lane minimum; otherwise every lane
     // keeps its own sorted top-KC (30 VGPRs at KC = 15) and the lanes are merged at the end
-    constexpr bool DIST = HDB_K1F_DIST && KC <= 16;
+    constexpr bool DIST = KC <= 16;
     double lv = INFINITY;
     double top[KC];
 #pragma unroll
@@ -1639,7 +1612,7 @@ static bool knn_mfma_dp(hdb_ctx *ctx, const double *X, int64_t n, int d, int KC,
     double *prm = (double *)take(256);
     unsigned long long *stats = (unsigned long long *)take(256);
     float *cst = (float *)take(4 * (size_t)(n_cap / 32) * S_CST);
-    int *log_cnt = (int *)take(8 * (size_t)n_cap);  // per query, or per half-query (HDB_K1S_REGTOP)
+    int *log_cnt = (int *)take(8 * (size_t)n_cap);  // per query, or per half-query (register top lists, KC <= 15)
     float *thr_f = (float *)take(4 * (size_t)n_cap);
     hipStream_t st = ctx->stream;
     hipLaunchKernelGGL(col_stats_kernel, dim3(nb), dim3(256), 0, st, X, n, d, nb, psum, pmax);
@@ -1714,13 +1687,11 @@ static bool knn_mfma_dp(hdb_ctx *ctx, const double *X, int64_t n, int d, int KC,
         if (prune) {
             // the layout-order FP64 copy (8 n DP bytes, ~2 GB at C4) only speeds the re-check:
             // when the device cannot hold it, the re-check reads the caller-order rows instead
-            if (HDB_K1F_LAYOUT) {
-                try {
-                    Xlay = (double *)arena(ctx, A_XLAY, 8 * (size_t)n_lp * DP);
-                } catch (const Error &) {
-                    (void)hipGetLastError();  // clear the failed allocation's sticky error
-                    Xlay = nullptr;
-                }
+            try {
+                Xlay = (double *)arena(ctx, A_XLAY, 8 * (size_t)n_lp * DP);
+            } catch (const Error &) {
+                (void)hipGetLastError();  // clear the failed allocation's sticky error
+                Xlay = nullptr;
             }
             const int g = (int)std::min<int64_t>(ceil_div(n_lp * 64, 256), 8192);
             hipLaunchKernelGGL(split_rows_kernel, dim3(g), dim3(256), 0, st, X, n, n_lp, d, DP, mu, prm, Xh, Xl, nrm2,
@@ -1796,7 +1767,7 @@ static bool knn_mfma_dp(hdb_ctx *ctx, const double *X, int64_t n, int d, int KC,
         ctx->stats["knn_mfma_group_rows"] = Cf::SQ;
         if (ctx->count_evals) {
             // diagnostic: logged candidates (the FP64 re-checks are those with lb <= thr)
-            const int nh = (HDB_K1S_REGTOP && KC <= 15) ? 2 : 1;
+            const int nh = KC <= 15 ? 2 : 1;
             std::vector<int> hc((size_t)n_lp * nh);
             HIP_CHECK(hipMemcpy(hc.data(), log_cnt, 4 * (size_t)n_lp * nh, hipMemcpyDeviceToHost));
             int64_t tot = 0;

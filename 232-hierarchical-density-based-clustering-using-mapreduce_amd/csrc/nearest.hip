@@ -244,9 +244,9 @@ static void stable_sort_by_key(hdb_ctx *ctx, const int32_t *keys, int64_t n, int
 // best sqrt value r, ties included), and candidates are kept by (sqrt value, sample index)
 // lexicographically -- the reference's first minimum in sample order (FirstStep.java:74-85),
 // whatever order the groups are scanned in.
-#ifndef HDB_NNG_SB
-#define HDB_NNG_SB 16  // K3g: consecutive sample groups tested behind one union box first (0: off; r04 C5 A/B nearest-sample phase: 2.69-2.73 s off, 2.18 at 4, 2.09-2.33 at 8, 2.07-2.09 at 16)
-#endif
+// K3g: consecutive sample groups tested behind one union box first (r04 C5 A/B nearest-sample
+// phase: 2.69-2.73 s with group boxes only, 2.18 at 4, 2.09-2.33 at 8, 2.07-2.09 at 16)
+constexpr int NNG_SB = 16;
 struct NNg {
     double r, g2;  // best sqrt value, pruning guard r^2 (1 + 2^-48)
     int i;
@@ -365,7 +365,9 @@ __global__ __launch_bounds__(256) void nng_search_kernel(const double *__restric
     // every group whose box can still reach the lane's best (wave-uniform loop).  sb > 0: runs of
     // sb consecutive groups (neighbours in the split tree) behind the union of their boxes, whose
     // bound is <= each member's (a larger box, the same monotone operations), so a run no lane
-    // can reach holds no group any lane would scan
+    // can reach holds no group any lane would scan.  The host always passes sb = NNG_SB, so the
+    // else arm (group boxes only) is not reached in this build; it stays so that the compiled
+    // kernel is the one that was measured.
     if (sb > 0) {
         for (int s0 = (w_lo / sb) * sb; s0 < w_hi; s0 += sb) {
             const bool need_s = live && s0 + sb > g_lo && s0 < g_hi && box_lb(sboxes + (int64_t)(s0 / sb) * 2 * D) <= b.g2;
@@ -486,9 +488,9 @@ static bool nearest_grouped(hdb_ctx *ctx, const double *X, int64_t n, const doub
     size_t tb = 0;
     HIP_CHECK(sort_pairs(nullptr, tb, (const uint32_t *)nullptr, (uint32_t *)nullptr, (const int32_t *)nullptr,
                          (int32_t *)nullptr, n, 0, 32, st));
-    // runs of SB groups behind one union box (HDB_NNG_SB; 0: group boxes only)
-    const int SB = HDB_NNG_SB;
-    const int ns = SB > 0 ? (ng + SB - 1) / SB : 0;
+    // runs of SB groups behind one union box
+    constexpr int SB = NNG_SB;
+    const int ns = (ng + SB - 1) / SB;
     std::vector<double> hsb((size_t)std::max(ns, 1) * 2 * d);
     for (int s2 = 0; s2 < ns; s2++)
         for (int c = 0; c < d; c++) {

@@ -1141,6 +1141,10 @@ __global__ __launch_bounds__(BS) void prim_coop4_kernel(PrimIn in, int n, int se
     }
 }
 
+// the plain attempt's same-XCD exchange (prim_coop_xcd) is for Prims of at most this many
+// workgroups (one XCD: 32 CUs)
+constexpr int PRIM_XCD_MAX_WG = 32;
+
 template <int DM, bool FULL, int BS>
 static bool launch_coop4_bs(hdb_ctx *ctx, const PrimIn &in, int64_t o, int64_t n, int64_t eo, int self_edges,
                             int32_t *va, int32_t *vb, double *w) {
@@ -1175,7 +1179,7 @@ static bool launch_coop4_bs(hdb_ctx *ctx, const PrimIn &in, int64_t o, int64_t n
     int spread1 = 1, res0 = 0;
     void *args[] = {&L, &nn, &self_edges, &pva, &pvb, &pw, &gkey, &grow, &err, &spin, &spread1, &xcc, &res0};
     // same-XCD exchange for the plain attempt when its blocks fit one XCD (32 CUs)
-    const int spread = (ctx->prim_coop_xcd && nwg <= ctx->prim_coop_xcd_max_wg && nwg <= 32 * per_cu) ? 8 : 1;
+    const int spread = (ctx->prim_coop_xcd && nwg <= PRIM_XCD_MAX_WG && nwg <= 32 * per_cu) ? 8 : 1;
     static std::atomic<int> launches{0};
     const int res = spread > 1 ? (launches.fetch_add(1) & 7) : 0;
     // A plain launch first: ROCm serialises cooperative launches device-wide, so the concurrent
@@ -1217,7 +1221,7 @@ static bool launch_coop4_bs(hdb_ctx *ctx, const PrimIn &in, int64_t o, int64_t n
 }
 
 // workgroup size: 1024 by default; prim_coop_bs = 0 takes the smallest of 128..1024 that keeps
-// the Prim within prim_coop_xcd_max_wg workgroups (one XCD), so more CUs -- and fewer waves per
+// the Prim within PRIM_XCD_MAX_WG workgroups (one XCD), so more CUs -- and fewer waves per
 // SIMD -- share each step's relaxation
 template <int DM, bool FULL>
 static bool launch_coop4(hdb_ctx *ctx, const PrimIn &in, int64_t o, int64_t n, int64_t eo, int self_edges,
@@ -1226,7 +1230,7 @@ static bool launch_coop4(hdb_ctx *ctx, const PrimIn &in, int64_t o, int64_t n, i
     if (bs == 0) {
         bs = 1024;
         for (int b = 128; b < 1024; b *= 2)
-            if (ceil_div(n, (int64_t)b) <= ctx->prim_coop_xcd_max_wg) {
+            if (ceil_div(n, (int64_t)b) <= PRIM_XCD_MAX_WG) {
                 bs = b;
                 break;
             }
@@ -1819,7 +1823,7 @@ static bool launch_spec(hdb_ctx *ctx, const PrimIn &in, int64_t o, int64_t n, in
     int spread1 = 1, res0 = 0;
     void *args[] = {&L, &nn, &self_edges, &pva, &pvb, &pw, &gcand, &gviol, &err, &spin, &spread1, &xcc, &res0, &stats,
                     &gstop};
-    const int spread = (ctx->prim_coop_xcd && nwg <= ctx->prim_coop_xcd_max_wg && nwg <= 32 * per_cu) ? 8 : 1;
+    const int spread = (ctx->prim_coop_xcd && nwg <= PRIM_XCD_MAX_WG && nwg <= 32 * per_cu) ? 8 : 1;
     static std::atomic<int> launches{0};
     const int res = spread > 1 ? (launches.fetch_add(1) & 7) : 0;
     const unsigned plain_spin = 1u << ctx->prim_coop_plain_spin_log2;

@@ -41,9 +41,7 @@
 namespace hdb {
 
 constexpr int BT = 64;  // tile size (one wave)
-#ifndef CAND_UNROLL
-#define CAND_UNROLL 2  // candidate-loop unroll: LDS-broadcast latency vs VGPRs (occupancy)
-#endif
+constexpr int CAND_UNROLL = 2;  // candidate-loop unroll: LDS-broadcast latency vs VGPRs (occupancy)
 
 template <int D>
 struct Rec {
@@ -244,12 +242,8 @@ struct RecEmitF {
 // tag: a leaf visit skips a sub-group no lane needs (finer culling, same wave shape).
 constexpr int SG = 16;
 constexpr int NSG = BT / SG;
-#ifndef HDB_K1T_WPE  // waves per EU the D <= 3 K1t is compiled for (82 VGPRs free-running: 5)
-#define HDB_K1T_WPE 5
-#endif
-#ifndef HDB_BOR_WPE  // waves per EU the D <= 3 Boruvka scan is compiled for
-#define HDB_BOR_WPE 4
-#endif
+constexpr int K1T_WPE = 5;  // waves per EU the D <= 3 K1t is compiled for (82 VGPRs free-running: 5)
+constexpr int BOR_WPE = 4;  // waves per EU the D <= 3 Boruvka scan is compiled for
 
 template <int D>
 __global__ void tile_box_kernel(const Rec<D> *__restrict__ recs, int64_t n, double *__restrict__ tlo,
@@ -499,32 +493,19 @@ __global__ __launch_bounds__(256) void retag_kernel(Rec<D> *__restrict__ recs, i
     }
 }
 
-#ifndef HDB_BOR_REFRESH_LOG2
-#define HDB_BOR_REFRESH_LOG2 3  // K2b: re-read the component bound every 2^x node visits
-#endif
+constexpr int BOR_REFRESH_LOG2 = 3;  // K2b: re-read the component bound every 2^x node visits
 // K2b leaf publish: a better edge reaches the component bound at once, one DPP minimum and at
 // most one atomic per wave (A/B r04: per-lane atomics 4.35 ms, never 3.90, per wave 2.84 ms)
-#ifndef HDB_BOR_ROWS
-#define HDB_BOR_ROWS 1  // K2b leaf groups needed by few lanes: (query, candidate) pairs in 16-lane rows
-#endif
-#ifndef HDB_BOR_SHFL
-#define HDB_BOR_SHFL 0  // K2b rows: query values by lane shuffles instead of LDS (occupancy A/B)
-#endif
-#ifndef HDB_BOR_ROWS_MAX
-#define HDB_BOR_ROWS_MAX 8  // ... when at most this many lanes need the group (else the candidate loop; r04 A/B scan: 2.85 ms at 4, 2.81 at 8, 2.84 at 16, 2.97 at 32, 4.1 at 64; K1t at 8: 1.58 vs 1.56 ms at 16)
-#endif
+// K2b and K1t leaf groups needed by few lanes are evaluated as (query, candidate) pairs in
+// 16-lane rows, when at most ROWS_MAX lanes need the group (else the candidate loop; r04 A/B
+// scan: 2.85 ms at 4, 2.81 at 8, 2.84 at 16, 2.97 at 32, 4.1 at 64; K1t at 8: 1.58 vs 1.56 ms
+// at 16).  K2b's rows read the query values from LDS, K1t's by lane shuffles (the other way
+// round was measured for occupancy in both kernels, not kept).
+constexpr int BOR_ROWS_MAX = 8;
+constexpr int K1T_ROWS_MAX = 16;
 // (round 4 also batched all needed groups of a leaf into one set of row passes, filtered at the
 // leaf's start, each lane recomputing its passers' distances: scan 2.84 -> 2.94 ms, 2 VGPRs
 // spilled at the 128-VGPR cap; removed)
-#ifndef HDB_K1T_ROWS
-#define HDB_K1T_ROWS 1  // K1t leaf groups needed by few lanes: (query, candidate) pairs in 16-lane rows
-#endif
-#ifndef HDB_K1T_SHFL
-#define HDB_K1T_SHFL 1  // K1t rows: query values by lane shuffles instead of LDS (occupancy; 0: LDS)
-#endif
-#ifndef HDB_K1T_ROWS_MAX
-#define HDB_K1T_ROWS_MAX 16
-#endif
 #ifndef HDB_BOR_PROF
 #define HDB_BOR_PROF 0  // diagnostic build: per-wave cycle split of the K2b scan (stats boruvka_prof_*)
 #endif
@@ -725,7 +706,7 @@ __device__ __forceinline__ void publish_min(unsigned long long *arr, int32_t c, 
 }
 
 template <int D, bool STATS>
-__global__ __launch_bounds__(256, (D <= 3 ? HDB_BOR_WPE : 1)) void boruvka_bvh_kernel(const Rec<D> *__restrict__ recs, int64_t n, int64_t ntiles,
+__global__ __launch_bounds__(256, (D <= 3 ? BOR_WPE : 1)) void boruvka_bvh_kernel(const Rec<D> *__restrict__ recs, int64_t n, int64_t ntiles,
                                                           Bvh bvh, unsigned long long *__restrict__ comp_w,
                                                           double *__restrict__ best_w, double *__restrict__ best_s,
                                                           int32_t *__restrict__ best_lo, int32_t *__restrict__ best_hi,
@@ -744,21 +725,14 @@ __global__ __launch_bounds__(256, (D <= 3 ? HDB_BOR_WPE : 1)) void boruvka_bvh_k
     __shared__ int64_t lvl_s[4][2 * (MAXLEV + 1)];
     __shared__ double q_s[4][2 * D];
     __shared__ double sg_s[4][8 * 2 * D];
-#if HDB_BOR_ROWS
     // row-batched leaf groups: the wave's query points (staged once) and per group the needing
-    // lanes' bounds and the passing pairs' keys
-#if HDB_BOR_SHFL
-    // the query lanes' values come by lane shuffles (ds_bpermute) instead: 12 KB less LDS per
-    // workgroup (6 instead of 4 workgroups per CU)
-    __shared__ int32_t rq_lane[4][BT];
-#else
+    // lanes' bounds and the passing pairs' keys (query values by lane shuffles instead would
+    // save 12 KB of LDS per workgroup, 6 instead of 4 workgroups per CU: measured, not kept)
     __shared__ double rq_x[4][BT * D];
     __shared__ double rq_core[4][BT], rq_sb[4][BT];
     __shared__ int32_t rq_comp[4][BT], rq_id[4][BT], rq_lane[4][BT];
-#endif
     __shared__ double rk_w[4][BT], rk_s[4][BT];
     __shared__ int32_t rk_lo[4][BT], rk_hi[4][BT];
-#endif
     const int w = threadIdx.x >> 6;
     double *bxs = boxs_s[w];
     int32_t *bxt = boxt_s[w];
@@ -803,13 +777,11 @@ __global__ __launch_bounds__(256, (D <= 3 ? HDB_BOR_WPE : 1)) void boruvka_bvh_k
 #pragma unroll
         for (int c = 0; c < D; c++) mx[c] = 0;
     }
-#if HDB_BOR_ROWS && !HDB_BOR_SHFL
 #pragma unroll
     for (int c = 0; c < D; c++) rq_x[w][lane * D + c] = mx[c];
     rq_core[w][lane] = mcore;
     rq_comp[w][lane] = mcomp;
     rq_id[w][lane] = mid;
-#endif
     Best b{INFINITY, INFINITY, INT32_MAX, INT32_MAX};
     if (valid && best_w[i] < INFINITY) b = Best{best_w[i], best_s[i], best_lo[i], best_hi[i]};  // seed_kernel
     double cb2 = INFINITY;  // padded square of the component bound
@@ -939,7 +911,7 @@ __global__ __launch_bounds__(256, (D <= 3 ? HDB_BOR_WPE : 1)) void boruvka_bvh_k
         const int lev = code >> 26;
         const int64_t idx = code & ((1 << 26) - 1);
         const int64_t node = off_s[lev] + idx;
-        if ((visits++ & ((1 << HDB_BOR_REFRESH_LOG2) - 1)) == 0) refresh();
+        if ((visits++ & ((1 << BOR_REFRESH_LOG2) - 1)) == 0) refresh();
         prof.mark(1);
         // re-test the popped node with the current bound (its parent tested it when pushing)
         if (pop_test & 1) {
@@ -978,7 +950,6 @@ __global__ __launch_bounds__(256, (D <= 3 ? HDB_BOR_WPE : 1)) void boruvka_bvh_k
             if (!__any(need)) continue;
             const int q0 = gi * SG;
             const int nq = (int)min<int64_t>(SG, n - (idx * BT + q0));
-#if HDB_BOR_ROWS
             // Few lanes need the group (typically 3-5 of 64): the wave-uniform candidate loop
             // spends 16 iterations on all 64 lanes for them.  Instead the (needing lane,
             // candidate) pairs are laid out four queries x 16 candidates per wave instruction
@@ -989,17 +960,12 @@ __global__ __launch_bounds__(256, (D <= 3 ? HDB_BOR_WPE : 1)) void boruvka_bvh_k
             // best edge is the one the sequential loop finds.
             const unsigned long long M = __ballot(need);
             const int K = __popcll(M);
-            if (K <= HDB_BOR_ROWS_MAX) {
+            if (K <= BOR_ROWS_MAX) {
                 const int rank = __popcll(M & ((1ull << lane) - 1));
-#if HDB_BOR_SHFL
-                const double sb0 = sb;  // the group-start bound of every lane
-                if (need) rq_lane[w][rank] = lane;
-#else
                 if (need) {
-                    rq_sb[w][lane] = sb;
+                    rq_sb[w][lane] = sb;  // the group-start bound
                     rq_lane[w][rank] = lane;
                 }
-#endif
                 __builtin_amdgcn_wave_barrier();
                 const int row = lane >> 4, c = lane & 15;
                 const LRec<D> r = cand[q0 + c];  // the row's candidate (4-way LDS broadcast)
@@ -1007,21 +973,11 @@ __global__ __launch_bounds__(256, (D <= 3 ? HDB_BOR_WPE : 1)) void boruvka_bvh_k
                     const int qr = r0 + row;
                     const bool rowact = qr < K;
                     const int ql = rq_lane[w][rowact ? qr : 0];
-#if HDB_BOR_SHFL
-                    // every lane shuffles (the loop is wave-uniform): a shuffle inside the
-                    // divergent branch below would read inactive lanes
-                    double s2 = sq_diff(__shfl(mx[0], ql), r.x[0]);
-#pragma unroll
-                    for (int cc = 1; cc < D; cc++) s2 = s2 + sq_diff(__shfl(mx[cc], ql), r.x[cc]);
-                    const int32_t qcomp = __shfl(mcomp, ql), qid = __shfl(mid, ql);
-                    const double qsb = __shfl(sb0, ql), qc = __shfl(mcore, ql);
-#else
                     double s2 = sq_diff(rq_x[w][ql * D], r.x[0]);
 #pragma unroll
                     for (int cc = 1; cc < D; cc++) s2 = s2 + sq_diff(rq_x[w][ql * D + cc], r.x[cc]);
                     const int32_t qcomp = rq_comp[w][ql], qid = rq_id[w][ql];
                     const double qsb = rq_sb[w][ql], qc = rq_core[w][ql];
-#endif
                     const bool pair = rowact & (c < nq) & (r.comp != qcomp);
                     if (STATS) nev += pair ? 1 : 0;  // pair evaluated for a lane that needs it
                     const bool pass = pair & (s2 <= qsb);  // also drops NaN
@@ -1055,7 +1011,6 @@ __global__ __launch_bounds__(256, (D <= 3 ? HDB_BOR_WPE : 1)) void boruvka_bvh_k
                 }
                 continue;
             }
-#endif
             const int q1 = q0 + nq;
 #pragma unroll CAND_UNROLL
             for (int qq = q0; qq < q1; qq++) {
@@ -1617,7 +1572,7 @@ inline unsigned k1t_grid(int64_t ntiles, int xcb) {
 // wave-uniform broadcast reads, and each lane evaluates the exact FP64 squared distance in
 // the reference's order and feeds the register top-K network.
 template <int D, int K, bool IDX, bool STATS>
-__global__ __launch_bounds__(256, (D <= 3 ? HDB_K1T_WPE : 1)) void knn_tree_kernel(const Rec<D> *__restrict__ recs, int64_t n, int64_t ntiles,
+__global__ __launch_bounds__(256, (D <= 3 ? K1T_WPE : 1)) void knn_tree_kernel(const Rec<D> *__restrict__ recs, int64_t n, int64_t ntiles,
                                                        Bvh bvh, int excl, double *__restrict__ lists,
                                                        int32_t *__restrict__ nb_pos, double *__restrict__ nb_s,
                                                        int pop_test, int xcb, unsigned long long *__restrict__ stats) {
@@ -1627,17 +1582,11 @@ __global__ __launch_bounds__(256, (D <= 3 ? HDB_K1T_WPE : 1)) void knn_tree_kern
     __shared__ int32_t boxt_s[4][FAN];
     __shared__ int64_t lvl_s[4][2 * (MAXLEV + 1)];
     __shared__ double q_s[4][2 * D];
-#if HDB_K1T_ROWS
-#if HDB_K1T_SHFL
-    // the query lanes' coordinates, bounds and self ids come by lane shuffles (ds_bpermute): 10 KB
-    // less LDS per workgroup, 8 instead of 5 workgroups per CU
+    // row-batched leaf groups: the query lanes' coordinates, bounds and self ids come by lane
+    // shuffles (ds_bpermute), not staged in LDS: 10 KB less LDS per workgroup, 8 instead of 5
+    // workgroups per CU (the LDS variant was measured, not kept)
     __shared__ double kq_s[4][BT];
     __shared__ int32_t kq_lane[4][BT];
-#else
-    __shared__ double kq_x[4][BT * D], kq_thr[4][BT], kq_s[4][BT];
-    __shared__ int32_t kq_skip[4][BT], kq_lane[4][BT];
-#endif
-#endif
     const int w = threadIdx.x >> 6;
     int64_t *off_s = lvl_s[w], *cnt_s = lvl_s[w] + MAXLEV + 1;
     // (XCD-contiguous tile ranges were measured again in round 4: 1.56 -> 1.74 ms, not kept)
@@ -1670,13 +1619,6 @@ __global__ __launch_bounds__(256, (D <= 3 ? HDB_K1T_WPE : 1)) void knn_tree_kern
     }
     const int32_t skip_self = excl ? mid : -2;
     unsigned long long nev = 0, n_leaf = 0, n_node = 0;
-#if HDB_K1T_ROWS
-#if !HDB_K1T_SHFL
-#pragma unroll
-    for (int c = 0; c < D; c++) kq_x[w][lane * D + c] = mx[c];
-    kq_skip[w][lane] = skip_self;
-#endif
-#endif
 
     auto needs_vals = [&](const double (&a)[D], const double (&b)[D], int32_t) -> bool {
         return valid & (box_lb2v<D>(mx, a, b) < buf[K - 1]);
@@ -1710,7 +1652,6 @@ __global__ __launch_bounds__(256, (D <= 3 ? HDB_K1T_WPE : 1)) void knn_tree_kern
             if (j1 <= j0) break;
             nev += (unsigned long long)(j1 - j0);
             const int q0 = gi * SG, q1 = q0 + (int)(j1 - j0);
-#if HDB_K1T_ROWS
             // few lanes need this group (not the own tile): the (needing lane, candidate) pairs
             // in 16-lane rows against the group-start K-th values (only looser: a rejected
             // candidate fails the insertion test at its turn too), the passers inserted by their
@@ -1719,17 +1660,10 @@ __global__ __launch_bounds__(256, (D <= 3 ? HDB_K1T_WPE : 1)) void knn_tree_kern
                 const bool need = gneeds(gi);
                 const unsigned long long M = __ballot(need);
                 const int Kn = __popcll(M);
-                if (Kn <= HDB_K1T_ROWS_MAX) {
+                if (Kn <= K1T_ROWS_MAX) {
                     const int rank = __popcll(M & ((1ull << lane) - 1));
-#if HDB_K1T_SHFL
                     const double thr0 = buf[K - 1];  // the group-start K-th value of every lane
                     if (need) kq_lane[w][rank] = lane;
-#else
-                    if (need) {
-                        kq_thr[w][lane] = buf[K - 1];
-                        kq_lane[w][rank] = lane;
-                    }
-#endif
                     __builtin_amdgcn_wave_barrier();
                     const int row = lane >> 4, c = lane & 15;
                     const LRec<D> r = cand[q0 + c];
@@ -1737,18 +1671,13 @@ __global__ __launch_bounds__(256, (D <= 3 ? HDB_K1T_WPE : 1)) void knn_tree_kern
                         const int qr = r0 + row;
                         const bool rowact = qr < Kn;
                         const int ql = kq_lane[w][rowact ? qr : 0];
-#if HDB_K1T_SHFL
+                        // every lane shuffles (the loop is wave-uniform): a shuffle inside a
+                        // divergent branch would read inactive lanes
                         double s2 = sq_diff(__shfl(mx[0], ql), r.x[0]);
 #pragma unroll
                         for (int cc = 1; cc < D; cc++) s2 = s2 + sq_diff(__shfl(mx[cc], ql), r.x[cc]);
                         const bool pass = rowact & (q0 + c < q1) & (r.id != __shfl(skip_self, ql)) &
                                           (s2 < __shfl(thr0, ql));
-#else
-                        double s2 = sq_diff(kq_x[w][ql * D], r.x[0]);
-#pragma unroll
-                        for (int cc = 1; cc < D; cc++) s2 = s2 + sq_diff(kq_x[w][ql * D + cc], r.x[cc]);
-                        const bool pass = rowact & (q0 + c < q1) & (r.id != kq_skip[w][ql]) & (s2 < kq_thr[w][ql]);
-#endif
                         if (pass) kq_s[w][lane] = s2;
                         const unsigned long long pm = __ballot(pass);
                         __builtin_amdgcn_wave_barrier();
@@ -1768,7 +1697,6 @@ __global__ __launch_bounds__(256, (D <= 3 ? HDB_K1T_WPE : 1)) void knn_tree_kern
                     continue;
                 }
             }
-#endif
 #pragma unroll CAND_UNROLL
             for (int qq = q0; qq < q1; qq++) {
                 const LRec<D> r = cand[qq];  // uniform address -> LDS broadcast
@@ -2126,10 +2054,9 @@ static void boruvka_on_index(hdb_ctx *ctx, Spatial<D> &sp, int64_t n, char *extr
             if (kl && kl->done) HIP_CHECK(hipMemsetAsync(kl->done, 0, (size_t)n, st));  // no exact seeds
             return;
         }
-#ifndef HDB_SEED_MAX_BLOCKS
-#define HDB_SEED_MAX_BLOCKS 2048
-#endif
-        const int gs = (int)std::min<int64_t>(ceil_div(n, 256), HDB_SEED_MAX_BLOCKS);
+        // grid-stride cap (a one-lane-per-point grid measured flat, within noise; not kept)
+        constexpr int SEED_MAX_BLOCKS = 2048;
+        const int gs = (int)std::min<int64_t>(ceil_div(n, 256), SEED_MAX_BLOCKS);
 #define ROUND_SEED(KK)                                                                                                 \
     case KK:                                                                                                           \
         hipLaunchKernelGGL((round_seed_kernel<D, KK>), dim3(gs), dim3(256), 0, st, recs, pcomp, n, prev,              \

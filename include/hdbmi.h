@@ -60,6 +60,9 @@ extern "C" {
 typedef struct hdb_ctx hdb_ctx;
 
 /* ------------------------------------------------------------------ context */
+/* Environment read here: HDB_KERNEL_TIMING=1 (hdb_ctx_set_timing from birth) and
+ * HDB_OPTS="name=value,name=value", every pair applied with hdb_ctx_set_option; a malformed pair
+ * or one that call rejects fails the creation with its status (no context is returned). */
 int hdb_ctx_create(int device, hdb_ctx **out);
 void hdb_ctx_destroy(hdb_ctx *ctx);
 /* Run on a caller-owned hipStream_t (e.g. torch's current stream); NULL = the device's default

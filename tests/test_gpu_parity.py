@@ -421,10 +421,9 @@ def test_sort_edges_desc_large_stable(pkg, oracle):
 @pytest.mark.parametrize("p,r,levels", [(200_000, 200_001, 40), (300_000, 0, 7), (100_000, 290_000, 0),
                                          (60_000, 180_000, 3), (5_000, 20_000, 2)])
 def test_sort_edges_desc_runs(pkg, oracle, p, r, levels):
-    """the run-aware merge (non-decreasing prefix + radix-sorted rest, merged): a prefix with
-    heavy tie groups (levels > 0: weights on a grid, incl. -0.0 next to +0.0), a rest that ties
-    with it, no rest at all, and a prefix below the run threshold -- equal to the oracle's
-    stable sort"""
+    """the lists the reducers hand over (a non-decreasing prefix, then an unsorted rest): a prefix
+    with heavy tie groups (levels > 0: weights on a grid, incl. -0.0 next to +0.0), a rest that
+    ties with it, no rest at all, and a short prefix -- equal to the oracle's stable sort"""
     rng = np.random.default_rng(p + r)
     if levels:
         pw = np.sort(rng.integers(0, levels + 1, p)).astype(np.float64) * 0.5
@@ -769,7 +768,7 @@ def test_nearest_grouped_keyed(pkg, oracle):
 @pytest.mark.parametrize("d", [3, 8])
 def test_nearest_grouped_keyed_vs_oracle(pkg, oracle, d):
     """Keyed K3g (the per-subset levels of C3/C5): uneven key sizes, so the runs of consecutive
-    sample groups tested behind one union box (HDB_NNG_SB) straddle key boundaries, and a key
+    sample groups tested behind one union box (16 groups per run) straddle key boundaries, and a key
     without samples (index 0 / MAX, the Java init)."""
     rng = np.random.default_rng(50 + d)
     n = 24000

@@ -286,6 +286,68 @@ def test_k6_option_ranges(pkg, ctx):
             ctx.set_option(name, bad)
 
 
+# a child of its own: HDB_OPTS is read when a context is created, and this process has its contexts
+# already.  ctypes only (no torch import): a 5,000-edge tree in host arrays, K6 on the device
+# against the host algorithm, then two rejected settings.  One line per case on stdout.
+HDB_OPTS_CHILD = r"""
+import ctypes as C, os, sys
+import numpy as np
+L = C.CDLL(sys.argv[1])
+L.hdb_last_error.restype = C.c_char_p
+vp, i64 = C.c_void_p, C.c_int64
+L.hdb_flat_labels.argtypes = [vp, vp, vp, vp, i64, i64, C.c_int32, vp, vp]
+L.hdb_ctx_get_stat.argtypes = [vp, C.c_char_p, vp]
+L.hdb_ctx_destroy.argtypes = [vp]
+L.hdb_ctx_destroy.restype = None
+h = vp()
+rc = L.hdb_ctx_create(0, C.byref(h))
+assert rc == 0, (rc, L.hdb_last_error())
+m = 5000
+va = (np.arange(1, m + 1) // 2).astype(np.int32)  # vertex i hangs below i // 2
+vb = np.arange(1, m + 1, dtype=np.int32)
+w = np.arange(m, 0, -1).astype(np.float64)       # merged order: descending
+out = []
+for ctx in (h, None):
+    lab, k = np.zeros(m + 1, np.int32), i64()
+    rc = L.hdb_flat_labels(ctx, va.ctypes.data, vb.ctypes.data, w.ctypes.data, m, m + 1, 5, lab.ctypes.data, C.byref(k))
+    assert rc == 0, (rc, L.hdb_last_error())
+    out.append((k.value, lab))
+assert out[0][0] == out[1][0] and np.array_equal(out[0][1], out[1][1])
+st = {}
+for name in (b"flat_global_depths", b"flat_mid_depths"):
+    v = i64()
+    assert L.hdb_ctx_get_stat(h, name, C.byref(v)) == 0
+    st[name] = v.value
+print("depths", st[b"flat_global_depths"], st[b"flat_mid_depths"])
+L.hdb_ctx_destroy(h)
+for bad in sys.argv[2:]:
+    os.environ["HDB_OPTS"] = bad
+    h = vp()
+    print("rejected", L.hdb_ctx_create(0, C.byref(h)), h.value, L.hdb_last_error().decode())
+"""
+
+
+def test_hdb_opts_environment_goes_through_set_option(pkg):
+    """HDB_OPTS applies its pairs with hdb_ctx_set_option when a context is created: block log 9
+    reaches K6 (2^13 > 5000 edges, mid log 12: 1 global depth and 12 - 9 = 3 dc_mid depths; the
+    default block log 10 gives 2), and a value outside the option's range, an unknown name, a
+    pair without a value or a value beyond 64 bits (for an option with no range of its own)
+    fails the creation with HDB_EINVAL and no context"""
+    import os
+    import subprocess
+    import sys
+    bad_opts = ("flat_block_log=7", "no_such=1", "flat_block_log", "knn_tree_min_n=99999999999999999999")
+    env = dict(os.environ, HDB_OPTS="flat_block_log=9")
+    r = subprocess.run([sys.executable, "-c", HDB_OPTS_CHILD, pkg._capi.LIB_PATH, *bad_opts], capture_output=True,
+                       text=True, timeout=60, env=env)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = r.stdout.splitlines()
+    assert lines[0] == "depths 1 3", lines
+    assert len(lines) == 1 + len(bad_opts)
+    for line, bad in zip(lines[1:], bad_opts):
+        assert line.startswith(f"rejected {EINVAL} None HDB_OPTS: ") and bad in line, line
+
+
 # ------------------------------------------------------------- bubble statistics and cores
 @pytest.mark.parametrize("name", ["iris", "skin_bubbles2k", "blobs2k"])
 def test_bubble_stats_one_lane_per_bubble_golden(pkg, ctx, name):

@@ -1,6 +1,7 @@
 """K5 bubble core distances (bubble kNN + the stale-index epilogue) at C5's model size:
 16,384 bubbles x 8, minPts 4 -- chunked scan with event replay vs the one-thread-per-bubble
-scan (HDB_BUBBLE_SPLIT), equal results.  usage: python tools/bubble_knn_bench.py [b] [d]"""
+scan (option bubble_knn_split; HDB_OPTS=bubble_knn_split=0 sets it for a whole program), equal
+results.  usage: python tools/bubble_knn_bench.py [b] [d]"""
 import importlib
 import os
 import sys

@@ -16,10 +16,9 @@ X = torch.from_numpy(make_blobs(n, d, 20, 1)).cuda()
 ctx = pkg.Context.get(0); ctx.use_torch_stream()
 star = pkg.HDBSCANStar(ctx)
 res = {"n": n, "d": d}
-for opt in os.environ.get("HDB_OPTS", "").split(","):
+for opt in os.environ.get("HDB_OPTS", "").split(","):  # applied by the library when ctx was created
     if opt:
         k, v = opt.split("=")
-        ctx.set_option(k, int(v))
         res[k] = int(v)
 
 
