@@ -92,11 +92,11 @@ struct hdb_ctx {
     bool bubble_knn_split = true;  // K5: candidate range in chunks + merge (one thread per bubble is 256 waves at 16k)
     bool prim_coop_xcd = true;     // plain attempt: working blocks on one XCD exchange through its L2 (checked at run time)
                                    // (for Prims of at most PRIM_XCD_MAX_WG workgroups, prim.hip)
-    int prim_coop_bs = 1024;  // cooperative Prim (slots 4/5) workgroup size; 0: the smallest of 128..1024 that keeps
+    int prim_coop_bs = 1024;  // cooperative Prim (slots 4) workgroup size; 0: the smallest of 128..1024 that keeps
                               // the Prim within PRIM_XCD_MAX_WG workgroups (more CUs share a step's relaxation)
     int prim_coop_plain_spin_log2 = 20;  // plain attempt: polls per exchange before it reports non-co-residency
-    int prim_coop_slots = 4;  // cooperative Prim exchange, rows in registers (d <= 16): 1 release/acquire slots, 2 granules,
-                              // 3 drained sc1 slots, 4 DPP folds + key granules (default), 5 key+row granule sweep
+    int prim_coop_slots = 4;  // cooperative Prim: 4 rows in registers (d <= 16), DPP folds + tagged key/row granules;
+                              // 0 the counter-barrier kernel for every d (also the fallback of 4); nothing else
     int flat_link_variant = 1;  // K6 dc_link A/B: 0 direct guarded atomics, 1 LDS-combined multi-batch
     int flat_root_variant = 3;  // K6 dc_root A/B: 0 LDS table (256 threads), 1 (1024), 2 direct atomics, 3-5 multi-batch
     bool flat_relabel = true;  // K6: divide-and-conquer vertex labels in rank order (locality; false: point ids)
@@ -122,7 +122,6 @@ enum {
 };
 
 void *arena(hdb_ctx *ctx, int slot, size_t bytes);
-bool hdb_prim_spec_built();  // prim.hip: the speculative Prim (slots 6) is in this build
 constexpr int PINNED_WORDS = 512;
 int64_t *pinned_words(hdb_ctx *ctx);
 // grow-only pinned host buffer (synchronises the stream before it grows)

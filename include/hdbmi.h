@@ -99,9 +99,9 @@ int hdb_ctx_synchronize(hdb_ctx *ctx);
  *                                  "prim_coop_xcd" (default 1: the plain attempt's working
  *                                  workgroups, when the run-time XCC_ID check finds them on one
  *                                  XCD, exchange through that XCD's L2 -- placement changes only
- *                                  speed), "prim_coop_slots" (exchange layout; 6: the speculative
- *                                  multi-step kernel, bit-exact, faster alone, slower when several
- *                                  Prims share the GPU);
+ *                                  speed), "prim_coop_slots" (default 4: rows of d <= 16 in registers,
+ *                                  tagged-granule exchange; 0: the counter-barrier kernel for every
+ *                                  d, which 4 also falls back to; any other value is HDB_EINVAL);
  *   "bubble_knn_split"(default 1): bubble core distances scan their candidates in chunks and
  *                                  replay the sequential insertion log exactly;
  *   "boruvka_seed"    (default 1): a Boruvka round starts from the previous round's still

@@ -570,9 +570,7 @@ def test_prim_cooperative_vs_oracle(pkg, oracle, n, kind):
     va, vb, w = oracle.prim_mst(X, core)
     ctx = pkg.Context.get(0)
     star = pkg.HDBSCANStar(ctx)
-    for coop, slots in ((1, 6), (1, 5), (1, 4), (1, 3), (1, 2), (1, 1), (1, 0), (0, 0)):
-        if not _slots_built(pkg, slots):
-            continue
+    for coop, slots in ((1, 4), (1, 0), (0, 0)):
         ctx.set_option("prim_coop", coop)
         ctx.set_option("prim_coop_slots", slots)
         try:
@@ -593,54 +591,23 @@ def test_prim_coop_plain_timeout_retries_cooperatively(pkg, oracle):
     ctx = pkg.Context.get(0)
     star = pkg.HDBSCANStar(ctx)
     before = ctx.get_stat("prim_coop_plain_retries")
-    for slots in (4, 5, 6):
-        if not _slots_built(pkg, slots):
-            continue
-        ctx.set_option("prim_coop_slots", slots)
-        ctx.set_option("prim_coop_plain_spin_log2", 0)
-        try:
-            g = star.constructMST(X, core, True)
-        finally:
-            ctx.set_option("prim_coop_plain_spin_log2", 20)
-            ctx.set_option("prim_coop_slots", 4)
-        assert eq(g.getVerticeA(), va) and eq(g.getVericeB(), vb) and eq(g.getEges(), w), slots
+    ctx.set_option("prim_coop_slots", 4)
+    ctx.set_option("prim_coop_plain_spin_log2", 0)
+    try:
+        g = star.constructMST(X, core, True)
+    finally:
+        ctx.set_option("prim_coop_plain_spin_log2", 20)
+    assert eq(g.getVerticeA(), va) and eq(g.getVericeB(), vb) and eq(g.getEges(), w)
     assert ctx.get_stat("prim_coop_plain_retries") >= before + 1
 
 
-@pytest.mark.parametrize("slots", [4, 6])
 @pytest.mark.parametrize("d,metric,n", [(8, "euclidean", 9000), (16, "euclidean", 5000), (5, "cosine", 6000),
                                         (2, "manhattan", 4500), (8, "euclidean", 16384), (3, "euclidean", 65536)])
-def test_prim_coop_slots_metrics_and_bubbles(pkg, oracle, d, metric, n, slots):
-    """The step-tagged cooperative Prim (rows in registers, d <= 16; slots 4) and the
-    speculative one (slots 6: many steps per exchange, undone past the first wrong pick) equal
-    the reference Prim for every metric, and the bubble Prim (HdbscanDataBubbles.java:165-254,
-    the C3/C5 bubble models they were written for) on > 4096 bubbles, up to 64 workgroups."""
-    _need_slots(pkg, slots)
-    pkg.Context.get(0).set_option("prim_coop_slots", slots)
-    try:
-        _coop_slots_case(pkg, oracle, d, metric, n)
-    finally:
-        pkg.Context.get(0).set_option("prim_coop_slots", 4)
-
-
-def _slots_built(pkg, slots):
-    """slots 6 (the speculative Prim) exists only in a -DHDB_PRIM_SPEC=1 build"""
-    c = pkg.Context.get(0)
-    try:
-        c.set_option("prim_coop_slots", slots)
-    except pkg.HdbError:
-        return False
-    finally:
-        c.set_option("prim_coop_slots", 4)
-    return True
-
-
-def _need_slots(pkg, slots):
-    if not _slots_built(pkg, slots):
-        pytest.skip("speculative Prim not built (HDBMI_EXTRA_FLAGS=-DHDB_PRIM_SPEC=1)")
-
-
-def _coop_slots_case(pkg, oracle, d, metric, n):
+def test_prim_coop_slots_metrics_and_bubbles(pkg, oracle, d, metric, n):
+    """The cooperative Prim with its rows in registers (d <= 16; slots 4) equals the reference
+    Prim for every metric, and the bubble Prim (HdbscanDataBubbles.java:165-254, the C3/C5 bubble
+    models it was written for) on > 4096 bubbles, up to 64 workgroups."""
+    pkg.Context.get(0).set_option("prim_coop_slots", 4)
     X = blobs(n, d, 9, n + d, spread=20.0)
     core = oracle.core_distances(X, 4, metric=metric, semantics=0)
     ids = (np.arange(n, dtype=np.int32) * 3 + 1)

@@ -422,7 +422,7 @@ def test_prim_coop_workgroup_size_xcd_and_launch_kind(pkg, ctx, star, oracle, n,
     size (0: the smallest of 128..1024 that keeps the Prim within 32 workgroups, launch_coop4),
     the XCD spread factor of the plain attempt (8 when the workgroups fit one XCD), one
     cooperative-Prim launch per call.  More than 64 workgroups (9000 rows at 128) are outside
-    the kernel's exchange layout: launch_coop4_bs declines and the slot kernel runs."""
+    the kernel's exchange layout: launch_coop4_bs declines and the counter-barrier kernel runs."""
     X, ids, core, bub, (va, vb, w) = prim_case(oracle, n, kind)
     model = pkg.HdbscanDataBubbles(ctx)
     for bs in (0, 128, 256, 512, 1024):
@@ -447,6 +447,47 @@ def test_prim_coop_workgroup_size_xcd_and_launch_kind(pkg, ctx, star, oracle, n,
                     spread = 8 if (plain and xcd and nwg <= 32 and not retried) else 1
                     assert ctx.get_stat("prim_coop_last_spread") == spread, what
     print(f"n={n} {kind}: prim_coop_bs=0 ran {next((b for b in (128, 256, 512) if -(-n // b) <= 32), 1024)} threads per workgroup")
+
+
+def test_prim_coop_slots_accepts_only_4_and_0(pkg, ctx, star, oracle):
+    """every other prim_coop_slots value is HDB_EINVAL and leaves the option at 4: the next call
+    runs the register kernel (the counter-barrier kernel of slots 0 does not count a launch)"""
+    for v in (-1, 1, 2, 3, 5, 6, 7):
+        with pytest.raises(pkg.HdbError) as ei:
+            ctx.set_option("prim_coop_slots", v)
+        assert ei.value.code == EINVAL, v
+    X, ids, core, _, (va, vb, w) = prim_case(oracle, 4097, "points")
+    before = ctx.get_stat("prim_coop_launches")
+    g = star.constructMST(X, core, True, None, ids)
+    assert ctx.get_stat("prim_coop_launches") == before + 1
+    assert bits_eq(g.getVerticeA(), va) and bits_eq(g.getVericeB(), vb) and bits_eq(g.getEges(), w)
+
+
+def test_prim_coop_rows_wider_than_the_register_kernel(pkg, timed, oracle):
+    """d = 17 has no prim_coop4_kernel instantiation (rows of d <= 16 in registers), n = 4097 is the
+    smallest cooperative size: under the default options points and bubbles take the
+    counter-barrier kernel, one launch each and no stepwise launches, and give the reference
+    Prim's edges in its order"""
+    ctx, n, d = timed, 4097, 17
+    rng = np.random.default_rng(n + d)
+    X = blobs(n, d, 9, n + d, spread=20.0)
+    ids = np.arange(n, dtype=np.int32) * 3 + 1
+    eB, nnB = np.abs(rng.normal(0.3, 0.1, n)), np.abs(rng.normal(0.2, 0.05, n))
+    nB = rng.integers(1, 9, n).astype(np.int32)
+    core = oracle.core_distances(X, 4, semantics=0)
+    bcore = oracle.bubble_core_distances(X, nB, eB, nnB, 4)
+    runs = (("points", lambda: pkg.HDBSCANStar(ctx).constructMST(X, core, True, None, ids),
+             oracle.prim_mst(X, core, ids)),
+            ("bubbles", lambda: pkg.HdbscanDataBubbles(ctx).constructMSTBubbles(X, nB, eB, nnB, ids, bcore, True),
+             oracle.bubble_prim_mst(X, eB, nnB, bcore, ids)))
+    for kind, run, (va, vb, w) in runs:
+        before = ctx.get_stat("prim_coop_launches")
+        for k in ("prim_coop", "prim_step_total"):
+            ctx.kernel_time(k)
+        g = run()
+        assert bits_eq(g.getVerticeA(), va) and bits_eq(g.getVericeB(), vb) and bits_eq(g.getEges(), w), kind
+        assert ctx.get_stat("prim_coop_launches") == before, kind
+        assert (ctx.kernel_time("prim_coop")[1], ctx.kernel_time("prim_step_total")[1]) == (1, 0), kind
 
 
 # ------------------------------------------------------------ popped-node re-tests (K1t, K2b)

@@ -1,5 +1,6 @@
 """Cooperative Prim step cost: bubble Prim (HdbscanDataBubbles.constructMSTBubbles) and the
-plain reference Prim at n points, d dims, with and without the step-tagged slots.
+plain reference Prim at n points, d dims, with the register kernel (prim_coop_slots 4) and the
+counter-barrier kernel (0).
 usage: python tools/coop_bench.py [n] [d]"""
 import importlib
 import os
@@ -23,7 +24,7 @@ ids = torch.arange(n, dtype=torch.int32).cuda()
 ctx = pkg.Context.get(0)
 ctx.use_torch_stream()
 star, model = pkg.HDBSCANStar(ctx), pkg.HdbscanDataBubbles(ctx)
-for slots in (5, 4, 1):
+for slots in (4, 0):
     ctx.set_option("prim_coop_slots", slots)
     for name, f in (("prim", lambda: star.constructMST(X, core, True, None, ids)),
                     ("bubble_prim", lambda: model.constructMSTBubbles(X, nB, eB, nnB, ids, core, True))):

@@ -1,4 +1,4 @@
-"""Phase timestamps of the cooperative Prim (coop2, prim_coop_slots = 3) from a build with
+"""Phase timestamps of the cooperative Prim (prim_coop4_kernel, prim_coop_slots = 4) from a build with
 -DHDB_COOP_PROF (HDBMI_EXTRA_FLAGS=-DHDB_COOP_PROF HDBMI_OUT=lib_prof build_lib.py; run with
 HDBMI_LIB=.../lib_prof/libhdbmi.so).  Prints the median cycles between phases of steps
 1024..1087 of workgroup 0.  usage: python tools/coop_prof.py [n] [d]"""
@@ -23,7 +23,6 @@ ids = torch.arange(n, dtype=torch.int32).cuda()
 ctx = pkg.Context.get(0)
 ctx.use_torch_stream()
 star = pkg.HDBSCANStar(ctx)
-ctx.set_option("prim_coop_slots", int(os.environ.get("SLOTS", "4")))
 if os.environ.get("BUBBLES"):
     rngb = np.random.default_rng(1)
     eB = torch.from_numpy(np.abs(rngb.normal(0.3, 0.1, n))).cuda()
@@ -44,7 +43,7 @@ print(f"n={n} d={d} cycles/step median {np.median(t[1:, 0] - t[:-1, 0]):.0f}")
 for j in range(5):
     print(f"  {names[j]:22s} median {np.median(dif[:, j]):7.0f}  p90 {np.percentile(dif[:, j], 90):7.0f}")
 print(f"  {names[5]:22s} median {np.median(nxt):7.0f}")
-if np.any(t8[:, 6]):  # slots 4/5 kernels: relaxation / wave minimum split of phase 0
+if np.any(t8[:, 6]):  # relaxation / wave minimum split of phase 0
     print(f"    relax (mrd + key)      median {np.median(t8[:, 6] - t8[:, 0]):7.0f}")
     print(f"    wave min + last lane   median {np.median(t8[:, 7] - t8[:, 6]):7.0f}")
     print(f"    park + barrier         median {np.median(t8[:, 1] - t8[:, 7]):7.0f}")

@@ -49,14 +49,7 @@ for rep in range(2):
             if key in out:
                 assert all(np.array_equal(a, b) for a, b in zip(out[key], e)), f"{name}: edges differ with xcd={xcd}"
             out[key] = e
-            try:
-                sr = ctx.get_stat("prim_spec_rounds")
-                spec = f"  spec rounds {sr} steps {ctx.get_stat('prim_spec_steps')} cyc " + " ".join(
-                    str(ctx.get_stat("prim_spec_cyc_" + k)) for k in ("list", "spec", "exch", "commit")) + \
-                    f" exec {ctx.get_stat('prim_spec_exec_w0')} {ctx.get_stat('prim_spec_exec_w1')}"
-            except Exception:
-                spec = ""
             print(f"xcd={xcd} {name:12s} n={n} d={d}: {dt * 1e3:8.2f} ms  ({dt / n * 1e6:.2f} us/step)  "
-                  f"retries {ctx.get_stat('prim_coop_plain_retries') - r0}{spec}", flush=True)
+                  f"retries {ctx.get_stat('prim_coop_plain_retries') - r0}", flush=True)
 ctx.set_option("prim_coop_xcd", 1)
 print("edges identical across xcd settings")
