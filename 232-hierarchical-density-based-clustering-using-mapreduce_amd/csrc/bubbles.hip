@@ -35,6 +35,11 @@ __global__ void bubble_count_kernel(const int32_t *__restrict__ bo, int64_t n, i
     }
 }
 
+// Math.pow(x, e) for the exponents the int division 1 / d leaves, 0 (d > 1) and 1 (d = 1): Java
+// defines both results exactly -- 1.0 for any x, NaN included, and x itself -- and the device's
+// pow(x, 1.0) is not x in the last bit for some x = 1 / n (the nnDist of d = 1 bubbles)
+__device__ __forceinline__ double jpow01(double x, int e) { return e == 0 ? 1.0 : x; }
+
 // K4 fold, one lane per (bubble, dimension): a coordinate's LS and SS are two independent
 // sequential chains over the bubble's members (ascending id, D5), kept in registers -- the same
 // additions in the same order as the per-bubble fold, bit for bit.  nb x d lanes instead of nb
@@ -97,7 +102,7 @@ __global__ void bubble_epilogue_kernel(int d, const int64_t *__restrict__ off, i
             extent = extent / d;
             I[0] = extent;
             // computeNNDistBubble (:42-44): pow(1/n, (int)(1/d)) * extent
-            I[1] = pow((1 / n), (double)(1 / d)) * extent;
+            I[1] = jpow01((1 / n), 1 / d) * extent;
             I[2] = n;
         } else {
             const int32_t n = (int32_t)cnt;
@@ -107,7 +112,7 @@ __global__ void bubble_epilogue_kernel(int d, const int64_t *__restrict__ off, i
             for (int c = 0; c < d; c++) sum = sum + (((2 * n * Q[c]) - (2 * (L[c] * L[c]))) / prod);
             const double extent = sqrt(sum);
             I[0] = extent;
-            I[1] = pow((double)1 / n, (double)1 / d) * extent;
+            I[1] = (d == 1 ? (double)1 / n : pow((double)1 / n, (double)1 / d)) * extent;
             I[2] = n;
         }
     }
@@ -159,7 +164,7 @@ __global__ void bubble_fold_kernel(const double *__restrict__ X, int d, const in
             extent = extent / d;
             I[0] = extent;
             // computeNNDistBubble (:42-44): pow(1/n, (int)(1/d)) * extent
-            I[1] = pow((1 / n), (double)(1 / d)) * extent;
+            I[1] = jpow01((1 / n), 1 / d) * extent;
             I[2] = n;
         } else {
             const int32_t n = (int32_t)cnt;
@@ -169,7 +174,7 @@ __global__ void bubble_fold_kernel(const double *__restrict__ X, int d, const in
             for (int c = 0; c < d; c++) sum = sum + (((2 * n * Q[c]) - (2 * (L[c] * L[c]))) / prod);
             const double extent = sqrt(sum);
             I[0] = extent;
-            I[1] = pow((double)1 / n, (double)1 / d) * extent;
+            I[1] = (d == 1 ? (double)1 / n : pow((double)1 / n, (double)1 / d)) * extent;
             I[2] = n;
         }
     }

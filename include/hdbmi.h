@@ -228,7 +228,22 @@ int hdb_exact_mst(hdb_ctx *ctx, const double *X, int64_t n, int32_t d, int32_t m
  * FirstStep.call non-leaf branch (FirstStep.java:74-85): the FIRST minimum over the sample
  * list (strict '<').  With x_key/s_key non-NULL only samples of the point's key are scanned
  * (D3; ClusterFeaturesByNodesMapper.java:53-61).  nearest_out = list position (0 if no
- * candidate, as the Java init), dist_out nullable (Double.MAX_VALUE if none). */
+ * candidate, as the Java init), dist_out nullable (Double.MAX_VALUE if none).
+ *
+ * Degenerate and non-finite input (every path gives the reference's result, bit for bit):
+ *  - A (point, sample) pair whose distance is NaN (a NaN coordinate, inf - inf, a cosine or Pearson
+ *    of rows whose norm or variance is 0, underflows or overflows) or is not below Double.MAX_VALUE
+ *    (an infinite coordinate, a squared distance that overflows) is no candidate: the reference's
+ *    'distance < minDistance' from Double.MAX_VALUE never holds for it.
+ *  - A point without any candidate -- a NaN row, every sample out of range, a key without samples
+ *    -- gets list position 0 and Double.MAX_VALUE.  Position 0 is also a legitimate winner: only
+ *    dist_out tells the two apart.
+ *  - Distances compare as sqrt values; among equal sqrt values (also from different squares, and
+ *    when every squared distance underflows to 0) the smaller list position wins.
+ *  - The grouped scan (K3g; option nearest_grouped) runs for Euclidean distance, d in {2, 3, 4, 8,
+ *    16}, n >= 8192 points and m >= 1024 samples, and only when every sample coordinate is finite.
+ *    Any NaN or infinite SAMPLE, like any other shape, metric or nearest_grouped = 0, takes the
+ *    plain scan.  Non-finite POINTS go through either path. */
 int hdb_nearest_sample(hdb_ctx *ctx, const double *X, int64_t n, const double *S, int64_t m, int32_t d,
                        int32_t metric, const int32_t *x_key, const int32_t *s_key, int32_t *nearest_out,
                        double *dist_out);
@@ -236,7 +251,22 @@ int hdb_nearest_sample(hdb_ctx *ctx, const double *X, int64_t n, const double *S
 /* --------------------------------------------------------- bubble statistics (a11, a12)
  * Bulk CombineStep (CombineStep.java:18-64) over a partition: member order = ascending
  * point index (D5).  Outputs per bubble: ls, ss, rep (nb*d), info (nb*3: extent, nnDist, n).
- * Empty bubbles: all zero. */
+ * Empty bubbles: all zero.  A one-member bubble: rep = the row, extent = nnDist = 0.
+ *
+ * Degenerate and non-finite input (the same for hdb_bubble_partials + hdb_bubble_combine; both
+ * fold kernels, option bubble_fold_dim, give the same bits):
+ *  - ls and ss are the sequential sums in member order; ss may overflow to +inf, ls may become
+ *    NaN (+inf and -inf members) and both carry a member's NaN.  rep = ls / n as it comes out.
+ *  - HDB_BUBBLE_COMBINESTEP: a dimension adds sqrt(v / (n (n - 1))) to the extent only when
+ *    v = 2 n SS - 2 LS^2 satisfies v >= 0 (CombineStep.java:46-56).  A negative v (rounding noise of
+ *    members that agree to a few ulps) and a NaN v (inf - inf after an overflow, a non-finite
+ *    member) add nothing, so the extent is never NaN; it is 0 when no dimension qualifies and
+ *    +inf when a v is +inf.  v is computed without contraction: a fused multiply-add changes its
+ *    sign on such members.
+ *  - HDB_BUBBLE_CF sums v / (n (n - 1)) over the dimensions without the test and takes one sqrt
+ *    (ClusterFeatureDataBubbles.java:192-215): a negative or NaN sum gives a NaN extent and nnDist.
+ *    n (n - 1) is a Java int and wraps: exact up to n = 46,341, negative from 46,342 on (NaN
+ *    extent), 0 at n = 65,536 (division by zero: NaN or inf), as the reference computes it. */
 int hdb_bubble_stats(hdb_ctx *ctx, const double *X, int64_t n, int32_t d, const int32_t *bubble_of, int64_t nb,
                      int32_t variant, double *ls, double *ss, double *rep, double *info);
 
@@ -248,7 +278,8 @@ int hdb_bubble_stats(hdb_ctx *ctx, const double *X, int64_t n, int32_t d, const 
  * and hdb_bubble_combine merges the gathered partials of all slices in slice order (empty
  * partials skipped) and computes rep / extent / nnDist from the merged (LS, SS, n) with
  * CombineStep.java:42-64's formulas.  One slice is hdb_bubble_stats(HDB_BUBBLE_COMBINESTEP)
- * bit for bit. */
+ * bit for bit.  Degenerate and non-finite members: as documented at hdb_bubble_stats (the sign test
+ * on v runs once, on the merged sums; an empty slice between two others changes nothing). */
 int hdb_bubble_partials(hdb_ctx *ctx, const double *X, int64_t n, int32_t d, const int32_t *bubble_of, int64_t nb,
                         const int64_t *cuts, int32_t S, double *part_ls, double *part_ss, double *part_n);
 int hdb_bubble_combine(hdb_ctx *ctx, const double *part_ls, const double *part_ss, const double *part_n, int32_t S,
@@ -256,12 +287,24 @@ int hdb_bubble_combine(hdb_ctx *ctx, const double *part_ls, const double *part_s
 
 /* ------------------------------------------------------------- bubble model (a13-a15)
  * HdbscanDataBubbles.calculateCoreDistancesBubbles(double[][] repB, int[] nB, double[] eB,
- * double[] nnDistB, int k, DistanceCalculator) (HdbscanDataBubbles.java:75-76). */
+ * double[] nnDistB, int k, DistanceCalculator) (HdbscanDataBubbles.java:75-76).
+ *
+ * Degenerate statistics: the k-NN buffer starts at Double.MAX_VALUE and a neighbour enters on a
+ * strict '<', so a bubble pair whose transformed distance is NaN (a NaN rep, a NaN nnDist) or is
+ * not below Double.MAX_VALUE (an infinite rep or extent) is no candidate, and a bubble with fewer
+ * than minPts - 1 candidates keeps Double.MAX_VALUE entries that the core formula then reads.
+ * Extent 0 and nnDist 0 (one-member bubbles, identical members) are ordinary values: equal
+ * distances keep the first neighbour in index order.  The chunked scan (option bubble_knn_split)
+ * and the plain scan give the same bits. */
 int hdb_bubble_core_distances(hdb_ctx *ctx, const double *rep, const int32_t *nB, const double *eB,
                               const double *nnB, int64_t b, int32_t d, int32_t min_pts, int32_t metric,
                               double *core_out);
 
-/* HdbscanDataBubbles.constructMSTBubbles(...) (HdbscanDataBubbles.java:165-167). */
+/* HdbscanDataBubbles.constructMSTBubbles(...) (HdbscanDataBubbles.java:165-167).
+ * Degenerate statistics: the reference's Prim, edge for edge in its order.  A candidate weight
+ * that is NaN or not below Double.MAX_VALUE never relaxes a vertex; a vertex that no comparison
+ * relaxed is attached with weight Double.MAX_VALUE, in the reference's order, by every kernel
+ * here (block, cooperative register, cooperative counter-barrier). */
 int hdb_bubble_prim_mst(hdb_ctx *ctx, const double *rep, const double *eB, const double *nnB,
                         const int32_t *id_bubbles, const double *core, int64_t b, int32_t d, int32_t metric,
                         int32_t self_edges, int32_t *va, int32_t *vb, double *w);
