@@ -573,4 +573,70 @@ int hdb_flat_outlier_scores(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, 
     });
 }
 
+int64_t hdb_cluster_tree_bound(int64_t n, int32_t min_cl_size) { return cluster_tree_bound(n, min_cl_size); }
+
+int hdb_flat_cluster_tree(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, const double *w, int64_t ne,
+                          int64_t n, int32_t min_cl_size, int64_t cap, int64_t *n_tree, int32_t *parent,
+                          double *birth, double *death, double *stability, int32_t *size, int32_t *min_id,
+                          int32_t *flat_label, int32_t *point_cluster, double *point_level, int64_t *n_clusters) {
+    const bool bad = ne < 0 || n < 0 || cap < 0 || !n_tree || (ne > 0 && (!va || !vb || !w));
+    if (!ctx) {  // host-only use (all pointers in host memory): no device needed
+        try {
+            if (bad) HDB_THROW(HDB_EINVAL, "bad arguments");
+            const ClusterTreeOut t{cap, n_tree, parent, birth, death, stability, size, min_id, flat_label,
+                                   point_cluster, point_level};
+            return flat_cluster_tree_host(va, vb, w, ne, n, min_cl_size, t, nullptr, n_clusters);
+        } catch (const Error &e) {
+            set_error(e.msg);
+            return e.code;
+        } catch (const std::bad_alloc &) {
+            set_error("host allocation failed");
+            return HDB_ENOMEM;
+        }
+    }
+    return guarded(ctx, [&] {
+        if (bad) HDB_THROW(HDB_EINVAL, "bad arguments");
+        Stager sg(ctx);
+        const int32_t *da = sg.in(va, (size_t)ne), *db = sg.in(vb, (size_t)ne);
+        const double *dw = sg.in(w, (size_t)ne);
+        // staged per-cluster outputs are sized by what the tree can hold, not by a generous cap
+        const size_t nk = (size_t)std::min<int64_t>(cap, cluster_tree_bound(n, std::max<int32_t>(min_cl_size, 2)));
+        const size_t np = (size_t)n;
+        ClusterTreeOut t{(int64_t)nk, n_tree, sg.out(parent, nk), sg.out(birth, nk), sg.out(death, nk),
+                         sg.out(stability, nk), sg.out(size, nk), sg.out(min_id, nk), sg.out(flat_label, nk),
+                         sg.out(point_cluster, np), sg.out(point_level, np)};
+        flat_cluster_tree_device(ctx, da, db, dw, ne, n, min_cl_size, t, n_clusters);
+        sg.finish();
+    });
+}
+
+int hdb_labels_at_levels(hdb_ctx *ctx, const int32_t *parent, const double *birth, int64_t K,
+                         const int32_t *point_cluster, const double *point_level, int64_t n,
+                         const double *levels, int32_t L, int32_t *labels_out) {
+    const bool bad = K < 0 || n < 0 || L < 0 || (L > 0 && !levels) || (K > 0 && (!parent || !birth)) ||
+                     (n > 0 && (!point_cluster || !point_level)) || (n > 0 && L > 0 && !labels_out);
+    if (!ctx) {  // host-only use (all pointers in host memory): no device needed
+        try {
+            if (bad) HDB_THROW(HDB_EINVAL, "bad arguments");
+            return labels_at_levels_host(parent, birth, K, point_cluster, point_level, n, levels, L, labels_out);
+        } catch (const Error &e) {
+            set_error(e.msg);
+            return e.code;
+        } catch (const std::bad_alloc &) {
+            set_error("host allocation failed");
+            return HDB_ENOMEM;
+        }
+    }
+    return guarded(ctx, [&] {
+        if (bad) HDB_THROW(HDB_EINVAL, "bad arguments");
+        Stager sg(ctx);
+        const int32_t *dp = sg.in(parent, (size_t)K), *dpc = sg.in(point_cluster, (size_t)n);
+        const double *db = sg.in(birth, (size_t)K), *dpl = sg.in(point_level, (size_t)n);
+        const double *dlv = sg.in(levels, (size_t)L);
+        int32_t *dout = sg.out(labels_out, (size_t)L * (size_t)n);
+        labels_at_levels_device(ctx, dp, db, K, dpc, dpl, n, dlv, L, dout);
+        sg.finish();
+    });
+}
+
 }  // extern "C"

@@ -16,11 +16,15 @@
 //   3. FOSC propagation children-before-parents, then one pass labels the points;
 //   4. on request, the GLOSH outlier scores (HDBSCANStar.java:505-540, 653-686): step 2 records
 //      where each point leaves and each cluster's lowest level, one pass children-before-parents
-//      propagates the levels, one pass scores the points.
+//      propagates the levels, one pass scores the points;
+//   5. on request, the condensed cluster tree itself (hdb_flat_cluster_tree): the clusters of
+//      step 2 under canonical tree labels, root first, then (birth descending, smallest member
+//      ascending), with where and when each point leaves.
 // O(E log E + n) host work; the inputs may live in HBM (staged once).
 #include <algorithm>
 #include <limits>
 #include <numeric>
+#include <string>
 #include <vector>
 
 #include "internal.hpp"
@@ -59,10 +63,13 @@ struct Clu {
 
 // labels / n_clusters: the flat partition (labels nullable).  scores / noise (nullable): GLOSH
 // outlier scores and eps(x) from the same hierarchy (see flat_outlier_scores_host below).
+// tree (nullable): the cluster tree's arrays (flat_cluster_tree_host).
 int flat_host_impl(const int32_t *va, const int32_t *vb, const double *w, int64_t ne, int64_t n, int32_t mcs,
-                   int32_t *labels, int64_t *n_clusters, double *scores, double *noise) {
+                   int32_t *labels, int64_t *n_clusters, double *scores, double *noise,
+                   const ClusterTreeOut *tree = nullptr) {
     if (n <= 0) {
         if (n_clusters) *n_clusters = 0;
+        if (tree) *tree->n_tree = 0;
         return HDB_OK;
     }
     if (mcs < 2) HDB_THROW(HDB_EINVAL, "flat labels: minClSize must be >= 2");
@@ -146,7 +153,7 @@ int flat_host_impl(const int32_t *va, const int32_t *vb, const double *w, int64_
     // outlier scores: a point leaves (becomes noise) at the reached node whose invalid child
     // holds it -- eps(x) = that node's level, last(x) = that node's cluster; a cluster's own
     // lowest level is the level of the last node on its chain (levels fall along it)
-    const bool want_scores = scores != nullptr;
+    const bool want_scores = scores != nullptr || tree != nullptr;
     std::vector<double> eps_pt, death;
     std::vector<int32_t> last_pt, sub;
     if (want_scores) {
@@ -241,10 +248,42 @@ int flat_host_impl(const int32_t *va, const int32_t *vb, const double *w, int64_
     }
     if (n_clusters) *n_clusters = (int64_t)sel.size();
 
+    // ---- 5. the cluster tree under canonical labels: 1 = the root, 2.. by (birth level
+    // descending, smallest member ascending) -- total, since clusters born at one level are
+    // disjoint; a parent is born above its children, so its label is the smaller one
+    if (tree) {
+        *tree->n_tree = nc;
+        if (tree->cap < nc)
+            HDB_THROW(HDB_EINVAL, "cluster tree: capacity " + std::to_string(tree->cap) + " is below the " +
+                                      std::to_string(nc) + " clusters of the tree");
+        std::vector<int32_t> order((size_t)nc), newlab((size_t)nc), flat_of((size_t)nc, 0);
+        std::iota(order.begin(), order.end(), 0);
+        std::sort(order.begin() + 1, order.end(), [&](int32_t a, int32_t b) {
+            return cl[a].birth > cl[b].birth || (cl[a].birth == cl[b].birth && cl[a].minid < cl[b].minid);
+        });
+        for (int64_t i = 0; i < nc; i++) newlab[order[i]] = (int32_t)(i + 1);
+        for (size_t i = 0; i < sel.size(); i++) flat_of[sel[i]] = (int32_t)(i + 1);
+        auto level = [](double x) { return x == 0.0 ? 0.0 : x; };  // -0.0 and 0.0 are one level
+        for (int64_t i = 0; i < nc; i++) {
+            const int32_t c = order[i];
+            if (tree->parent) tree->parent[i] = c ? newlab[cl[c].parent] : 0;
+            if (tree->birth) tree->birth[i] = level(cl[c].birth);
+            if (tree->death) tree->death[i] = level(death[c]);
+            if (tree->stability) tree->stability[i] = cl[c].stab;
+            if (tree->size) tree->size[i] = (int32_t)nodes[cl[c].node].size;
+            if (tree->min_id) tree->min_id[i] = cl[c].minid;
+            if (tree->flat_label) tree->flat_label[i] = flat_of[c];
+        }
+        for (int64_t v = 0; v < n; v++) {
+            if (tree->point_cluster) tree->point_cluster[v] = newlab[last_pt[v]];
+            if (tree->point_level) tree->point_level[v] = level(eps_pt[v]);
+        }
+    }
+
     // ---- 4. GLOSH: eps_max(C) = the lowest level among C and its descendants
     // (Cluster.propagate's propagatedLowestChildDeathLevel, Cluster.java:99-105); the root
     // takes its descendants only and keeps Double.MAX_VALUE when it never splits
-    if (want_scores) {
+    if (scores) {
         std::vector<double> eps_max(death);
         eps_max[0] = std::numeric_limits<double>::max();
         for (int64_t c = nc - 1; c >= 1; c--) eps_max[cl[c].parent] = std::min(eps_max[cl[c].parent], eps_max[c]);
@@ -270,6 +309,42 @@ int flat_labels_host(const int32_t *va, const int32_t *vb, const double *w, int6
 int flat_outlier_scores_host(const int32_t *va, const int32_t *vb, const double *w, int64_t ne, int64_t n,
                              int32_t mcs, double *scores, double *noise, int32_t *labels, int64_t *n_clusters) {
     return flat_host_impl(va, vb, w, ne, n, mcs, labels, n_clusters, scores, noise);
+}
+
+// The condensed cluster tree of the hierarchy above (HDBSCANStar.computeHierarchyAndClusterTree
+// :208-474), canonical tree labels; labels and n_clusters as flat_labels_host (nullable).
+int flat_cluster_tree_host(const int32_t *va, const int32_t *vb, const double *w, int64_t ne, int64_t n,
+                           int32_t mcs, const ClusterTreeOut &tree, int32_t *labels, int64_t *n_clusters) {
+    return flat_host_impl(va, vb, w, ne, n, mcs, labels, n_clusters, nullptr, nullptr, &tree);
+}
+
+// hierarchy rows at arbitrary levels: label(x, eps) = 0 below eps(x), else the first cluster on
+// the chain from last(x) to the root that is not born at or below eps (the root's NaN birth
+// stops the climb).  One top-down pass over the clusters per level (a parent's label is below
+// its children's), then one lookup per point.
+int labels_at_levels_host(const int32_t *parent, const double *birth, int64_t K, const int32_t *point_cluster,
+                          const double *point_level, int64_t n, const double *levels, int32_t L,
+                          int32_t *labels_out) {
+    if (K < 0 || n < 0 || L < 0) HDB_THROW(HDB_EINVAL, "bad arguments");
+    for (int32_t l = 0; l < L; l++)
+        if (levels[l] != levels[l]) HDB_THROW(HDB_EINVAL, "labels at levels: NaN level");
+    if (L == 0 || n == 0) return HDB_OK;
+    if (K >= INT32_MAX) HDB_THROW(HDB_EINVAL, "labels at levels: too many clusters");
+    if (K > 0 && parent[0] != 0) HDB_THROW(HDB_EINVAL, "labels at levels: the root (label 1) must have parent 0");
+    for (int64_t i = 1; i < K; i++)
+        if (parent[i] < 0 || parent[i] > i) HDB_THROW(HDB_EINVAL, "labels at levels: parent label out of range");
+    for (int64_t v = 0; v < n; v++)
+        if (point_cluster[v] < 1 || point_cluster[v] > K)
+            HDB_THROW(HDB_EINVAL, "labels at levels: point cluster out of range");
+    std::vector<int32_t> res((size_t)K + 1);
+    for (int32_t l = 0; l < L; l++) {
+        const double eps = levels[l];
+        res[0] = 0;
+        for (int64_t i = 0; i < K; i++) res[i + 1] = birth[i] <= eps ? res[parent[i]] : (int32_t)(i + 1);
+        int32_t *row = labels_out + (int64_t)l * n;
+        for (int64_t v = 0; v < n; v++) row[v] = eps < point_level[v] ? 0 : res[point_cluster[v]];
+    }
+    return HDB_OK;
 }
 
 }  // namespace hdb

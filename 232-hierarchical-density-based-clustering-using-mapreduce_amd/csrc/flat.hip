@@ -29,6 +29,11 @@
 //  5. on request (hdb_flat_outlier_scores), the GLOSH outlier scores from the same arrays:
 //     first valid ancestor per node (pointer jumping), each cluster's own lowest level (one
 //     store), subtree minima over the cluster tree (exact pointer doubling), a per-point pass.
+//  6. on request (hdb_flat_cluster_tree), the cluster tree itself under canonical tree labels:
+//     two small radix sorts renumber the clusters, one gather pass and one per-point pass
+//     write the arrays (section 7);
+//  7. hdb_labels_at_levels cuts such a tree at arbitrary levels: ancestor tables by binary
+//     lifting, one thread per point over the sorted levels (section 8).
 #include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
@@ -1736,6 +1741,212 @@ __global__ void gl_point_scores(const int32_t *__restrict__ pparent, const int32
     }
 }
 
+// ------------------------------------------------------------------ 7. cluster tree export
+// hdb_flat_cluster_tree: the clusters above under canonical tree labels (1 = the root, then birth
+// level descending, smallest member ascending), run only when the tree is asked for, after
+// gl_own_level (dw still holds each cluster's own lowest level) and with K on the host.
+
+// per cluster: its start node, and for the non-root clusters the two sort keys.  ew holds
+// canonical levels (-0.0 folded, tied weights bit-equal), so the inverted ordered key sorts
+// levels descending, not edge ranks.
+__global__ void ct_keys(const int32_t *__restrict__ is_start, const int32_t *__restrict__ cid,
+                        const int32_t *__restrict__ pnode, const int32_t *__restrict__ eminid,
+                        const double *__restrict__ ew, int64_t m, int32_t K, int32_t *__restrict__ cstart,
+                        uint32_t *__restrict__ kmin, unsigned long long *__restrict__ kbirth,
+                        int32_t *__restrict__ ids) {
+    HDB_GRID_STRIDE(r, m) {
+        if (!is_start[r]) continue;
+        const int32_t c = cid[r];
+        if ((uint32_t)c >= (uint32_t)K) continue;
+        cstart[c] = (int32_t)r;
+        if (c == K - 1) continue;  // the root goes first by rule
+        const int32_t P = pnode[r];
+        kmin[c] = (uint32_t)eminid[r];
+        kbirth[c] = ~ord_enc(ew[(uint32_t)P < (uint32_t)m ? P : r]);
+        ids[c] = c;
+    }
+}
+
+__global__ void ct_birth_keys(const unsigned long long *__restrict__ kbirth, const int32_t *__restrict__ ids,
+                              int32_t count, unsigned long long *__restrict__ out) {
+    HDB_GRID_STRIDE(i, count) out[i] = kbirth[ids[i]];
+}
+
+// inv[old cluster id] = tree label
+__global__ void ct_inverse(const int32_t *__restrict__ perm, int32_t K, int32_t *__restrict__ inv) {
+    HDB_GRID_STRIDE(i, K) inv[i == 0 ? K - 1 : perm[i - 1]] = (int32_t)i + 1;
+}
+
+struct TreeArr {
+    const int32_t *perm, *inv, *cstart, *cpar, *cminid, *pnode, *esize, *rk;
+    const double *ew, *stab;
+    const unsigned long long *dw;
+    const uint64_t *tw;
+    ClusterTreeOut o;
+    int32_t K;
+};
+
+// one gather pass: entry i = tree label i + 1 = old cluster perm[i - 1] (the root for i = 0)
+__global__ void ct_gather(TreeArr a) {
+    HDB_GRID_STRIDE(i, a.K) {
+        const int32_t c = i == 0 ? a.K - 1 : a.perm[i - 1];
+        const int32_t r = a.cstart[c];
+        const bool root = i == 0;
+        if (a.o.parent) a.o.parent[i] = root ? 0 : a.inv[a.cpar[c]];
+        if (a.o.birth) a.o.birth[i] = root ? (double)NAN : a.ew[a.pnode[r]];
+        if (a.o.death) a.o.death[i] = ord_dec(a.dw[c]);
+        if (a.o.stability) a.o.stability[i] = root ? (double)NAN : a.stab[c];  // NaN from the root's NaN birth
+        if (a.o.size) a.o.size[i] = a.esize[r];
+        if (a.o.min_id) a.o.min_id[i] = a.cminid[c];
+        if (a.o.flat_label) a.o.flat_label[i] = (!root && pk_hi(a.tw[c]) == c) ? a.rk[a.cminid[c]] + 1 : 0;
+    }
+}
+
+// per point: the cluster it leaves from and the level at which it leaves (gl_point_scores' reads)
+__global__ void ct_points(const int32_t *__restrict__ pparent, const int32_t *__restrict__ top,
+                          const int32_t *__restrict__ fva, const int32_t *__restrict__ cs,
+                          const int32_t *__restrict__ cid, const int32_t *__restrict__ inv,
+                          const double *__restrict__ ew, int64_t n, int32_t *__restrict__ point_cluster,
+                          double *__restrict__ point_level) {
+    HDB_GRID_STRIDE(v, n) {
+        const int32_t t = top[pparent[v]];
+        if (point_cluster) point_cluster[v] = inv[cid[cs[t]]];
+        if (point_level) point_level[v] = ew[fva[t]];
+    }
+}
+
+// n == 1: the root alone, no level
+__global__ void ct_single(ClusterTreeOut o) {
+    if (blockIdx.x || threadIdx.x) return;
+    if (o.parent) o.parent[0] = 0;
+    if (o.birth) o.birth[0] = (double)NAN;
+    if (o.death) o.death[0] = 0.0;
+    if (o.stability) o.stability[0] = 0.0;
+    if (o.size) o.size[0] = 1;
+    if (o.min_id) o.min_id[0] = 0;
+    if (o.flat_label) o.flat_label[0] = 0;
+    if (o.point_cluster) o.point_cluster[0] = 1;
+    if (o.point_level) o.point_level[0] = 0.0;
+}
+
+// ------------------------------------------------------------------ 8. level cuts
+// hdb_labels_at_levels: label(x, eps) = 0 below eps(x), else the first cluster on the chain from
+// last(x) to the root that is not born at or below eps.  The cluster tree can be thousands deep,
+// so the climb uses ancestor tables (binary lifting): anc[j][C] = the 2^j-th ancestor of tree
+// label C (0 = none), J = ceil(log2 K) rows of K + 1 ints.  birth rises strictly along a chain,
+// so "born at or below eps" holds on a prefix of it: gallop up the rows while it holds, then
+// descend over the lower rows -- O(log(steps climbed)) reads, all in a table that stays in the
+// L2.  The levels are visited in ascending order (one small radix sort; a row is stored at its
+// level's original index): the answer only moves rootwards as eps grows, so a point keeps its
+// current cluster and that cluster's birth in registers, a level that does not move it costs no
+// table read at all, and the climbs of all L levels together cover its chain once.  The input
+// tree is validated, never trusted: every index is bounded.
+enum : int { LE_PARENT = 1, LE_POINT = 2, LE_NAN = 4 };
+constexpr int CUT_TB = 256, CUT_CHUNK = 64;
+
+// row 0 (index 0 = "none" -> itself) and the birth table by label (index 0 = NaN: stops a climb)
+__global__ void lc_init(const int32_t *__restrict__ parent, const double *__restrict__ birth, int32_t K,
+                        int32_t *__restrict__ anc0, double *__restrict__ bt, int *__restrict__ err) {
+    int e = 0;
+    HDB_GRID_STRIDE(i, (int64_t)K + 1) {
+        int32_t p = 0;
+        double b = (double)NAN;
+        if (i > 0) {
+            p = parent[i - 1];
+            b = birth[i - 1];
+            if (p < 0 || p >= i || (i == 1 && p != 0)) {  // parent label in 0..label - 1; the root has none
+                e = LE_PARENT;
+                p = 0;
+            }
+        }
+        anc0[i] = p;
+        bt[i] = b;
+    }
+    flag_or(err, e);
+}
+
+__global__ void lc_double(const int32_t *__restrict__ prev, int32_t *__restrict__ next, int32_t K) {
+    HDB_GRID_STRIDE(i, (int64_t)K + 1) next[i] = prev[prev[i]];  // values are in 0..K by construction
+}
+
+// sort keys of the levels (ascending, -inf first) with their row indices; a NaN level is an error
+__global__ void lc_level_keys(const double *__restrict__ levels, int32_t L, unsigned long long *__restrict__ key,
+                              int32_t *__restrict__ row, int *__restrict__ err) {
+    int e = 0;
+    HDB_GRID_STRIDE(l, L) {
+        const double v = levels[l];
+        if (v != v) e = LE_NAN;
+        key[l] = ord_enc(v);
+        row[l] = (int32_t)l;
+    }
+    flag_or(err, e);
+}
+
+// one thread per point, the sorted levels through LDS in chunks (uniform across the wave:
+// broadcast reads), one row-contiguous store per (point, level)
+__global__ __launch_bounds__(CUT_TB) void lc_cut(const int32_t *__restrict__ anc, const double *__restrict__ bt,
+                                                 int32_t K, int J, const int32_t *__restrict__ point_cluster,
+                                                 const double *__restrict__ point_level, int64_t n,
+                                                 const unsigned long long *__restrict__ skey,
+                                                 const int32_t *__restrict__ srow, int32_t L,
+                                                 int32_t *__restrict__ out, int *__restrict__ err) {
+    __shared__ double lev[CUT_CHUNK];
+    __shared__ int32_t rowi[CUT_CHUNK];
+    const int64_t x = (int64_t)blockIdx.x * CUT_TB + threadIdx.x;
+    const int64_t stride = (int64_t)K + 1;
+    int e = 0;
+    int32_t c0 = 0;
+    double pl = 0.0;
+    if (x < n) {
+        c0 = point_cluster[x];
+        pl = point_level[x];
+        if (c0 < 1 || c0 > K) {
+            e = LE_POINT;
+            c0 = 0;  // label 0: NaN birth, no ancestors -- every row of this point is 0
+        }
+    }
+    // cur: the first cluster from last(x) towards the root not born at or below the levels seen
+    // so far (they ascend); bcur: its birth
+    int32_t cur = c0;
+    double bcur = bt[c0];
+    for (int32_t base = 0; base < L; base += CUT_CHUNK) {
+        const int cnt = L - base < CUT_CHUNK ? L - base : CUT_CHUNK;
+        __syncthreads();
+        if ((int)threadIdx.x < cnt) {
+            lev[threadIdx.x] = ord_dec(skey[base + threadIdx.x]);
+            const int32_t r = srow[base + threadIdx.x];
+            rowi[threadIdx.x] = (uint32_t)r < (uint32_t)L ? r : 0;
+        }
+        __syncthreads();
+        if (x >= n) continue;
+        for (int k = 0; k < cnt; k++) {
+            const double eps = lev[k];
+            int32_t c = 0;
+            if (!(eps < pl)) {
+                if (bcur <= eps) {
+                    int j = 0;
+                    int32_t last = cur;  // the highest ancestor known to be born at or below eps
+                    while (j < J) {
+                        const int32_t a = anc[j * stride + cur];
+                        if (!(bt[a] <= eps)) break;  // a == 0 has a NaN birth
+                        last = a;
+                        j++;
+                    }
+                    for (int jj = j - 2; jj >= 0; jj--) {
+                        const int32_t a = anc[jj * stride + last];
+                        if (bt[a] <= eps) last = a;
+                    }
+                    cur = anc[last];  // its parent: the first cluster not born at or below eps
+                    bcur = bt[cur];
+                }
+                c = cur;
+            }
+            out[(int64_t)rowi[k] * n + x] = c;
+        }
+    }
+    flag_or(err, e);
+}
+
 // zero-initialised FOSC block: nch, kcur, plen, maxld (+ counters), pwide, a spare (m ints
 // each: 24m bytes, so the u64 array after them is 8-byte aligned), hkey (m u64), 192 jump flags
 inline size_t fz_layout(int64_t m) { return (size_t)m * 24 + (size_t)m * 8 + 192 * 4; }
@@ -1756,12 +1967,14 @@ struct Carver {
 }  // namespace
 
 // labels-only (scores == nullptr: exactly the launches of K6) or with the outlier-score passes
-// of section 6 after them; labels and noise are nullable when scores are given
+// of section 6 after them; labels and noise are nullable when scores are given.  tree (nullable):
+// the export of section 7, between the own-level pass and the subtree minima.
 static void flat_device_impl(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, const double *w, int64_t ne,
                              int64_t n, int32_t mcs, int32_t *labels, int64_t *n_clusters, double *scores,
-                             double *noise) {
+                             double *noise, const ClusterTreeOut *tree = nullptr) {
     if (n <= 0) {
         if (n_clusters) *n_clusters = 0;
+        if (tree) *tree->n_tree = 0;
         return;
     }
     if (mcs < 2) HDB_THROW(HDB_EINVAL, "flat labels: minClSize must be >= 2");
@@ -1849,6 +2062,13 @@ static void flat_device_impl(hdb_ctx *ctx, const int32_t *va, const int32_t *vb,
         if (scores) HIP_CHECK(hipMemsetAsync(scores, 0, sizeof(double), st));  // no level: eps = 0, score 0
         if (noise) HIP_CHECK(hipMemsetAsync(noise, 0, sizeof(double), st));
         if (n_clusters) *n_clusters = 0;
+        if (tree) {
+            *tree->n_tree = 1;
+            if (tree->cap < 1) HDB_THROW(HDB_EINVAL, "cluster tree: capacity 0 is below the 1 clusters of the tree");
+            hipLaunchKernelGGL(ct_single, dim3(1), dim3(64), 0, st, *tree);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipStreamSynchronize(st));
+        }
         return;
     }
     const int g = grid_for(m);
@@ -2083,7 +2303,7 @@ static void flat_device_impl(hdb_ctx *ctx, const int32_t *va, const int32_t *vb,
     }
     hipLaunchKernelGGL(fo_labels, dim3(g), dim3(256), 0, st, tw, cminid, rk, Kp, clab, err);
     hipLaunchKernelGGL(fo_count, dim3(1), dim3(64), 0, st, mk, rk, n, (int64_t *)(words + 3), err);
-    if (!scores) {
+    if (!scores && !tree) {
         hipLaunchKernelGGL(fl_point_labels, dim3(grid_for(n)), dim3(256), 0, st, pparent, top, cs, cid, clab, n,
                            labels, err);
     } else {
@@ -2098,6 +2318,54 @@ static void flat_device_impl(hdb_ctx *ctx, const int32_t *va, const int32_t *vb,
         jump_all(fva, std::min(frounds, 64));
         hipLaunchKernelGGL(gl_own_level, dim3(g), dim3(256), 0, st, top, pnode, dc.esize, nvalid, cs, cid, cpar, Kp, ew,
                            m, mcs, dw, upa, groot, err);
+        if (tree) {
+            // ---- 7. the cluster tree, in scratch stages 1-3 are done with: keep/pos -> the
+            // permutation buffers, ca/cb -> the min-id keys, cw and lab -> the birth keys,
+            // hooked -> the inverse, parent -> the clusters' start nodes.  K comes to the host
+            // first (the capacity check, and the sorts' sizes).
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipMemcpyAsync(pin, words, sizeof(int64_t) * 4, hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipMemcpyAsync(pin + 4, Kp, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            const int et = (int)pin[1];
+            if (et & FE_CYCLE) HDB_THROW(HDB_EINVAL, "flat labels: the edges contain a cycle");
+            if (et & FE_ROOTS) HDB_THROW(HDB_EINVAL, "flat labels: the edges are not a spanning tree");
+            if (et & FE_JUMP) HDB_THROW(HDB_EDEVICE, "flat labels: pointer jumping did not converge in its launch budget");
+            const int32_t K = *(int32_t *)(pin + 4);
+            if (K < 1 || K > m) HDB_THROW(HDB_EDEVICE, "cluster tree: cluster count out of range");
+            *tree->n_tree = K;
+            if (tree->cap < K)
+                HDB_THROW(HDB_EINVAL, "cluster tree: capacity " + std::to_string(tree->cap) + " is below the " +
+                                          std::to_string(K) + " clusters of the tree");
+            int32_t *ids1 = keep, *ids2 = pos, *cstart = dc.parent, *inv = dc.hooked;
+            uint32_t *kmin1 = (uint32_t *)ca, *kmin2 = (uint32_t *)cb;
+            unsigned long long *kb1 = (unsigned long long *)cw, *kb2 = (unsigned long long *)dc.lab;
+            const int gk = grid_for(K);
+            hipLaunchKernelGGL(ct_keys, dim3(g), dim3(256), 0, st, is_start, cid, pnode, dc.eminid, ew, m, K, cstart,
+                               kmin1, kb1, ids1);
+            const int32_t *perm = ids1;
+            if (K > 2) {  // stable LSD: by smallest member first, then by birth level (descending)
+                const int64_t ks = K - 1;
+                size_t tb = 0, tb2 = 0;
+                HIP_CHECK(sort_pairs(nullptr, tb, kmin1, kmin2, ids1, ids2, ks, 0, 32, st));
+                HIP_CHECK(sort_pairs(nullptr, tb2, kb2, kb1, ids2, ids1, ks, 0, 64, st));
+                void *tmp = arena(ctx, A_FLAT_TMP, std::max(tb, tb2));
+                HIP_CHECK(sort_pairs(tmp, tb, kmin1, kmin2, ids1, ids2, ks, 0, 32, st));
+                hipLaunchKernelGGL(ct_birth_keys, dim3(gk), dim3(256), 0, st, kb1, ids2, (int32_t)ks, kb2);
+                HIP_CHECK(sort_pairs(tmp, tb2, kb2, kb1, ids2, ids1, ks, 0, 64, st));
+            }
+            hipLaunchKernelGGL(ct_inverse, dim3(gk), dim3(256), 0, st, perm, K, inv);
+            TreeArr ta{perm, inv, cstart, cpar, cminid, pnode, dc.esize, rk, ew, stab, dw, tw, *tree, K};
+            hipLaunchKernelGGL(ct_gather, dim3(gk), dim3(256), 0, st, ta);
+            if (tree->point_cluster || tree->point_level)
+                hipLaunchKernelGGL(ct_points, dim3(grid_for(n)), dim3(256), 0, st, pparent, top, fva, cs, cid, inv, ew,
+                                   n, tree->point_cluster, tree->point_level);
+        }
+        if (!scores) {
+            if (labels)
+                hipLaunchKernelGGL(fl_point_labels, dim3(grid_for(n)), dim3(256), 0, st, pparent, top, cs, cid, clab,
+                                   n, labels, err);
+        } else {
         // the cluster tree below the root's children is at most K - 2 < m deep and a round doubles
         // exactly: ceil(log2 m) rounds + one, whose flag must be zero
         int srounds = 2;
@@ -2110,6 +2378,7 @@ static void flat_device_impl(hdb_ctx *ctx, const int32_t *va, const int32_t *vb,
         hipLaunchKernelGGL(fl_jump_check, dim3(1), dim3(64), 0, st, jflags + srounds - 1, err);
         hipLaunchKernelGGL(gl_point_scores, dim3(grid_for(n)), dim3(256), 0, st, pparent, top, fva, cs, cid, clab, ew,
                            dw, groot, Kp, n, scores, noise, labels, err);
+        }
     }
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(pin, words, sizeof(int64_t) * 4, hipMemcpyDeviceToHost, st));
@@ -2133,6 +2402,68 @@ void flat_outlier_scores_device(hdb_ctx *ctx, const int32_t *va, const int32_t *
                                 int64_t *n_clusters) {
     if (n > 0 && !scores) HDB_THROW(HDB_EINVAL, "bad arguments");
     flat_device_impl(ctx, va, vb, w, ne, n, mcs, labels, n_clusters, scores, noise);
+}
+
+void flat_cluster_tree_device(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, const double *w, int64_t ne,
+                              int64_t n, int32_t mcs, const ClusterTreeOut &tree, int64_t *n_clusters) {
+    flat_device_impl(ctx, va, vb, w, ne, n, mcs, nullptr, n_clusters, nullptr, nullptr, &tree);
+}
+
+void labels_at_levels_device(hdb_ctx *ctx, const int32_t *parent, const double *birth, int64_t K,
+                             const int32_t *point_cluster, const double *point_level, int64_t n,
+                             const double *levels, int32_t L, int32_t *labels_out) {
+    if (K < 0 || n < 0 || L < 0) HDB_THROW(HDB_EINVAL, "bad arguments");
+    if (K >= (int64_t(1) << 30)) HDB_THROW(HDB_EINVAL, "labels at levels: too many clusters");
+    if (n > (int64_t(1) << 31) * (CUT_TB / 2)) HDB_THROW(HDB_EINVAL, "labels at levels: too many points");
+    hipStream_t st = ctx->stream;
+    KernelTimer tt(ctx, "labels_at_levels");
+    int J = 1;
+    while ((int64_t(1) << J) < K) J++;  // 2^J >= K > the deepest chain
+    const int64_t stride = K + 1;
+    Carver probe;
+    auto layout = [&](Carver &cv) {
+        cv.take<int64_t>(1);                  // error word
+        cv.take<double>(stride);              // births by label
+        cv.take<int32_t>(stride * J);         // ancestor rows
+        for (int k = 0; k < 2; k++) cv.take<unsigned long long>(L);  // level keys, sorted
+        for (int k = 0; k < 2; k++) cv.take<int32_t>(L);             // their rows
+    };
+    layout(probe);
+    Carver cv{(char *)arena(ctx, A_FLAT1, probe.off), 0};
+    int *err = (int *)cv.take<int64_t>(1);
+    double *bt = cv.take<double>(stride);
+    int32_t *anc = cv.take<int32_t>(stride * J);
+    unsigned long long *key1 = cv.take<unsigned long long>(L), *key2 = cv.take<unsigned long long>(L);
+    int32_t *row1 = cv.take<int32_t>(L), *row2 = cv.take<int32_t>(L);
+    HIP_CHECK(hipMemsetAsync(err, 0, sizeof(int64_t), st));
+    const int gk = grid_for(stride);
+    hipLaunchKernelGGL(lc_init, dim3(gk), dim3(256), 0, st, parent, birth, (int32_t)K, anc, bt, err);
+    for (int j = 1; j < J; j++)
+        hipLaunchKernelGGL(lc_double, dim3(gk), dim3(256), 0, st, anc + (j - 1) * stride, anc + j * stride, (int32_t)K);
+    if (L > 0) {  // also for n == 0: a NaN level is an error whatever n is
+        hipLaunchKernelGGL(lc_level_keys, dim3(grid_for(L)), dim3(256), 0, st, levels, L, key1, row1, err);
+        const unsigned long long *skey = key1;
+        const int32_t *srow = row1;
+        if (L > 1) {
+            size_t tb = 0;
+            HIP_CHECK(sort_pairs(nullptr, tb, key1, key2, row1, row2, L, 0, 64, st));
+            void *tmp = arena(ctx, A_FLAT_TMP, tb);
+            HIP_CHECK(sort_pairs(tmp, tb, key1, key2, row1, row2, L, 0, 64, st));
+            skey = key2, srow = row2;
+        }
+        if (n > 0)
+            hipLaunchKernelGGL(lc_cut, dim3((unsigned)ceil_div(n, (int64_t)CUT_TB)), dim3(CUT_TB), 0, st, anc, bt,
+                               (int32_t)K, J, point_cluster, point_level, n, skey, srow, L, labels_out, err);
+    }
+    HIP_CHECK(hipGetLastError());
+    int64_t *pin = pinned_words(ctx) + PINNED_WORDS - 8;
+    HIP_CHECK(hipMemcpyAsync(pin, err, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    const int e = (int)pin[0];
+    if (e & LE_NAN) HDB_THROW(HDB_EINVAL, "labels at levels: NaN level");
+    if (L == 0 || n == 0) return;  // as the host: the tree is not looked at
+    if (e & LE_PARENT) HDB_THROW(HDB_EINVAL, "labels at levels: parent label out of range");
+    if (e & LE_POINT) HDB_THROW(HDB_EINVAL, "labels at levels: point cluster out of range");
 }
 
 }  // namespace hdb

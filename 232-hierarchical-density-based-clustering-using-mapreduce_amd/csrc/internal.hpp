@@ -1,5 +1,7 @@
 // internal.hpp -- device-side building blocks shared by the C-ABI layer.
 #pragma once
+#include <algorithm>
+
 #include "common.hpp"
 
 namespace hdb {
@@ -82,6 +84,30 @@ void flat_outlier_scores_device(hdb_ctx *ctx, const int32_t *va, const int32_t *
                                 int64_t n, int32_t mcs, double *scores, double *noise, int32_t *labels,
                                 int64_t *n_clusters);
 
+// outputs of hdb_flat_cluster_tree: cap entries per cluster array, n per point array, each
+// nullable but n_tree (a host scalar); entry i describes tree label i + 1
+struct ClusterTreeOut {
+    int64_t cap;
+    int64_t *n_tree;
+    int32_t *parent;
+    double *birth, *death, *stability;
+    int32_t *size, *min_id, *flat_label;
+    int32_t *point_cluster;
+    double *point_level;
+};
+// K6 + the condensed cluster tree it builds, under canonical tree labels; synchronises
+void flat_cluster_tree_device(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, const double *w, int64_t ne,
+                              int64_t n, int32_t mcs, const ClusterTreeOut &tree, int64_t *n_clusters);
+// hierarchy rows (L x n) at arbitrary levels from a cluster tree, all arrays on the device; synchronises
+void labels_at_levels_device(hdb_ctx *ctx, const int32_t *parent, const double *birth, int64_t K,
+                             const int32_t *point_cluster, const double *point_level, int64_t n,
+                             const double *levels, int32_t L, int32_t *labels_out);
+// K <= max(1, 2 floor(n / mcs) - 1): disjoint leaves of >= mcs points, every split >= 2 ways
+inline int64_t cluster_tree_bound(int64_t n, int32_t mcs) {
+    if (n <= 0) return 0;
+    return std::max<int64_t>(1, 2 * (n / std::max<int32_t>(mcs, 1)) - 1);
+}
+
 // host logic (local_model.cpp)
 int bubble_core_epilogue(const double *rep, const int32_t *nB, const double *eB, const double *nnB, int64_t b, int d,
                          int min_pts, int metric, const double *knn, const int32_t *log, double *core);
@@ -89,6 +115,11 @@ int flat_labels_host(const int32_t *va, const int32_t *vb, const double *w, int6
                      int32_t *labels, int64_t *n_clusters);
 int flat_outlier_scores_host(const int32_t *va, const int32_t *vb, const double *w, int64_t ne, int64_t n,
                              int32_t mcs, double *scores, double *noise, int32_t *labels, int64_t *n_clusters);
+int flat_cluster_tree_host(const int32_t *va, const int32_t *vb, const double *w, int64_t ne, int64_t n,
+                           int32_t mcs, const ClusterTreeOut &tree, int32_t *labels, int64_t *n_clusters);
+int labels_at_levels_host(const int32_t *parent, const double *birth, int64_t K, const int32_t *point_cluster,
+                          const double *point_level, int64_t n, const double *levels, int32_t L,
+                          int32_t *labels_out);
 int quicksort_edges(int32_t *va, int32_t *vb, double *w, int64_t ne);
 // message of the last HDB_EREF_NEGATIVE_CLUSTER on this thread (cluster label, level, numPoints)
 const char *local_model_error_detail();

@@ -73,7 +73,7 @@ class MRHDBSCANStar:
                  seed=20210101, distanceFunction=None, all_inter_edges=True, max_levels=64, ctx=None,
                  device=0, flat_labels=True, profile=False, exact_prim_leaves=False, group=None,
                  prim_leaf_max=LEAF_PRIM_MAX, model_threads=4, defer_leaves=True, bubble_slices=BUBBLE_SLICES,
-                 emulate_ranks=(), cores_first=False, outlier_scores=False):
+                 emulate_ranks=(), cores_first=False, outlier_scores=False, cluster_tree=False):
         self.minPts = minPts
         self.minClSize = minClSize
         self.processing_units = processing_units
@@ -89,6 +89,10 @@ class MRHDBSCANStar:
         # GLOSH outlier scores with the flat labels, from the one hierarchy of a single combined
         # call (hdb_flat_outlier_scores); needs flat_labels and all_inter_edges
         self.outlier_scores = outlier_scores
+        # the condensed cluster tree (hdb_flat_cluster_tree) as out["cluster_tree"]; needs what
+        # outlier_scores needs.  One hierarchy call: the labels (and the scores, when asked for)
+        # are then re-derived from the tree, not from a second K6 pass
+        self.cluster_tree = cluster_tree
         self.profile = profile       # phase wall times (synchronising) in self.timings
         # True: every leaf, however large, runs the reference Prim (the exact edge list of
         # HDBSCANStar.constructMST, ties included; stepwise above 65,536 points).  False:
@@ -507,7 +511,16 @@ class MRHDBSCANStar:
             # System.exit(1) of Main.java:408); D7 makes the merged edges a spanning tree
             labels = torch.empty(n, dtype=torch.int32, device=dev)
             k = np.zeros(1, np.int64)
-            if self.outlier_scores:
+            if self.cluster_tree:
+                from .hdbscanstar import cluster_tree
+                tree = cluster_tree(va, vb, w, n, self.minClSize, ctx=c)
+                out["cluster_tree"] = tree
+                labels = tree.flat_labels()
+                k[0] = tree.n_clusters
+                if self.outlier_scores:
+                    out["outlier_scores"] = tree.outlier_scores()
+                    out["noise_levels"] = tree.point_level
+            elif self.outlier_scores:
                 scores = torch.empty(n, dtype=torch.float64, device=dev)
                 noise = torch.empty(n, dtype=torch.float64, device=dev)
                 A.check(A.lib().hdb_flat_outlier_scores(c.h, va.data_ptr(), vb.data_ptr(), w.data_ptr(), w.shape[0], n,

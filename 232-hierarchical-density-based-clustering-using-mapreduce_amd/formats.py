@@ -107,6 +107,66 @@ def format_outlier_scores(scores, ids) -> str:
     return "".join(f"{double_to_string(v)},{int(k)}\n" for v, k in zip(s, i))
 
 
+def hierarchy_levels(tree, compact: bool = True) -> np.ndarray:
+    """The levels the reference's hierarchy file has a row for, descending.  Every level
+    computeHierarchyAndClusterTree processes is the level of a reached node: the distinct values
+    of ``point_level`` together with ``birth[1:]``.  ``compact`` keeps the first level, every
+    birth level and every level whose predecessor in that list is a birth level -- the
+    ``!compactHierarchy || nextLevelSignificant || !newClusters.isEmpty()`` rule of
+    HDBSCANStar.java:394."""
+    t = tree.host()
+    births = np.asarray(t.birth[1:], dtype=np.float64) + 0.0
+    births = births[~np.isnan(births)]
+    allv = np.unique(np.concatenate([np.asarray(t.point_level, dtype=np.float64) + 0.0, births]))[::-1]
+    if not compact or allv.shape[0] == 0:
+        return np.ascontiguousarray(allv)
+    is_birth = np.isin(allv, births)
+    keep = is_birth.copy()
+    keep[0] = True
+    keep[1:] |= is_birth[:-1]
+    return np.ascontiguousarray(allv[keep])
+
+
+def format_hierarchy(tree, levels=None, compact: bool = True, ctx=None):
+    """The hierarchy file's text (HDBSCANStar.java:393-414, 436-442) and the cluster offsets
+    (``setFileOffset``, :419-421): one row ``level,l0,...,l(n-1)\\n`` per level (default:
+    ``hierarchy_levels(tree, compact)``) with the tree labels of ``labels_at_levels``, then the
+    closing row of n + 1 zeros.  Levels are written as ``Double.toString`` writes them.  Returns
+    ``(text, offsets)``: ``offsets[i]`` = the number of characters written through the row of
+    tree label i + 1's birth level (0 for the root, and for a birth level that has no row)."""
+    from .hdbscanstar import labels_at_levels
+    t = tree.host()
+    lv = hierarchy_levels(t, compact) if levels is None else np.ascontiguousarray(levels, dtype=np.float64)
+    rows = labels_at_levels(tree, lv, ctx=ctx)
+    rows = rows.detach().cpu().numpy() if hasattr(rows, "detach") else np.asarray(rows)
+    parts, written, through = [], 0, {}
+    for k in range(lv.shape[0]):
+        line = double_to_string(lv[k]) + "".join(f",{v}" for v in rows[k].tolist()) + "\n"
+        parts.append(line)
+        written += len(line)
+        through.setdefault(float(lv[k]) + 0.0, written)
+    parts.append(",".join(["0"] * (t.n + 1)) + "\n")
+    offsets = np.zeros(t.n_tree, dtype=np.int64)
+    for i in range(1, t.n_tree):
+        offsets[i] = through.get(float(t.birth[i]) + 0.0, 0)
+    return "".join(parts), offsets
+
+
+def format_cluster_tree(tree, offsets=None) -> str:
+    """The cluster-tree file's text (HDBSCANStar.java:449-468): one line
+    ``label,birth,death,stability,0,0,offset,parentLabel\\n`` per cluster in label order (the two
+    zeros are the constraint counts of a run without constraints); doubles as ``Double.toString``
+    writes them (``NaN`` for the root's birth and stability).  ``offsets``: the second result of
+    format_hierarchy (default: zeros)."""
+    t = tree.host()
+    off = np.zeros(t.n_tree, dtype=np.int64) if offsets is None else np.asarray(offsets, dtype=np.int64)
+    if off.shape[0] != t.n_tree:
+        raise ValueError("offsets must have one entry per cluster")
+    d = double_to_string
+    return "".join(f"{i + 1},{d(t.birth[i])},{d(t.death[i])},{d(t.stability[i])},0,0,{int(off[i])},{int(t.parent[i])}\n"
+                   for i in range(t.n_tree))
+
+
 def parse_local_mst(text):
     """UnionFindReducer.java:22-45: the records of one text value as arrays
     ``(va, vb, w, fake1, fake2, node)``."""

@@ -282,3 +282,130 @@ def outlier_ranking(scores, core):
         return np.ascontiguousarray(x, dtype=np.float64) + 0.0  # -0.0 + 0.0 == +0.0: one key per value
     s, c = host(scores), host(core)
     return np.lexsort((np.arange(s.shape[0]), c, s)).astype(np.int64)
+
+
+class ClusterTree:
+    """The condensed cluster tree of hdb_flat_cluster_tree.  Entry i of a per-cluster array
+    describes TREE LABEL i + 1 (1 = the root; 0 = noise / no parent): ``parent``, ``birth`` (NaN
+    for the root), ``death``, ``stability`` (NaN for the root), ``size``, ``min_id``,
+    ``flat_label`` (1..n_clusters when FOSC selected the cluster, else 0).  Per point:
+    ``point_cluster`` (the tree label the point leaves as noise from) and ``point_level`` (the
+    level at which it leaves, the noise level of outlier_scores).  Arrays are numpy arrays or
+    torch tensors, as the edges given to cluster_tree were."""
+
+    FIELDS = ("parent", "birth", "death", "stability", "size", "min_id", "flat_label", "point_cluster", "point_level")
+
+    def __init__(self, parent, birth, death, stability, size, min_id, flat_label, point_cluster, point_level,
+                 n_clusters):
+        self.parent, self.birth, self.death, self.stability = parent, birth, death, stability
+        self.size, self.min_id, self.flat_label = size, min_id, flat_label
+        self.point_cluster, self.point_level = point_cluster, point_level
+        self.n_clusters = int(n_clusters)
+
+    @property
+    def n_tree(self) -> int:
+        return int(self.parent.shape[0])
+
+    @property
+    def n(self) -> int:
+        return int(self.point_cluster.shape[0])
+
+    def host(self) -> "ClusterTree":
+        """The same record with numpy arrays."""
+        f = [getattr(self, k) for k in self.FIELDS]
+        return ClusterTree(*[x.detach().cpu().numpy() if A.is_torch(x) else np.asarray(x) for x in f], self.n_clusters)
+
+    def _t(self, name):
+        import torch
+        x = getattr(self, name)
+        return x if A.is_torch(x) else torch.from_numpy(np.ascontiguousarray(x))
+
+    def _back(self, t):
+        return t if A.is_torch(self.parent) else t.numpy()
+
+    def flat_labels(self):
+        """The flat partition of flat_labels, re-derived from the tree: flat_label of the nearest
+        selected cluster on the path from a point's last cluster to the root (pointer doubling
+        over the K clusters, one gather per point)."""
+        import torch
+        near, up, pc = self._t("flat_label").clone(), self._t("parent").to(torch.int64), self._t("point_cluster")
+        for _ in range(max(1, self.n_tree).bit_length()):
+            has = up > 0
+            idx = (up - 1).clamp(min=0)
+            near = torch.where((near == 0) & has, near[idx], near)
+            up = torch.where(has, up[idx], up)
+        if self.n == 0:
+            return self._back(pc.clone())
+        return self._back(near[pc.to(torch.int64) - 1])
+
+    def outlier_scores(self):
+        """The GLOSH scores of outlier_scores, re-derived from the tree (bit-identical): eps_max is
+        the subtree minimum of ``death`` (for the root: its descendants only, Double.MAX_VALUE
+        when it has none), score = 0 where point_level is 0, else 1 - eps_max / point_level."""
+        import torch
+        K = self.n_tree
+        em = self._t("death").clone()
+        par = self._t("parent").to(torch.int64)
+        if K:
+            em[0] = em[1:].min() if K > 1 else A.JMAX
+        up = torch.where(par <= 1, torch.zeros_like(par), par)  # nothing propagates into the root
+        while bool((up > 0).any()):
+            live = up > 0
+            em.scatter_reduce_(0, up[live] - 1, em[live], "amin")
+            up = torch.where(live, up[(up - 1).clamp(min=0)], up)
+        eps = self._t("point_level")
+        if self.n == 0:
+            return self._back(eps.clone())
+        e = em[self._t("point_cluster").to(torch.int64) - 1]
+        return self._back(torch.where(eps == 0, torch.zeros_like(eps), 1.0 - e / eps))
+
+
+def _flat_handle(a, ctx):
+    on_dev = a.device is not None and a.device.type == "cuda"
+    return ctx.h if ctx is not None else (A.Context.get(a.device.index or 0).h if on_dev else None)
+
+
+def cluster_tree_bound(n: int, minClSize: int) -> int:
+    """hdb_cluster_tree_bound: max(1, 2 * (n // minClSize) - 1) clusters at most (0 for n <= 0)."""
+    return int(A.lib().hdb_cluster_tree_bound(int(n), int(minClSize)))
+
+
+def cluster_tree(va, vb, w, n: int, minClSize: int, ctx=None) -> ClusterTree:
+    """The condensed cluster tree of the hierarchy flat_labels builds (HDBSCANStar.
+    computeHierarchyAndClusterTree :208-474; include/hdbmi.h hdb_flat_cluster_tree, DESIGN.md
+    "cluster tree"): a ClusterTree whose per-cluster arrays are sized with the bound and trimmed
+    to the K clusters found.  Tensors in give tensors out; device and host selection as in
+    flat_labels."""
+    a, b, ww = A.Arr(va, np.int32), A.Arr(vb, np.int32), A.Arr(w, np.float64)
+    cap = max(cluster_tree_bound(n, max(int(minClSize), 2)), 1)
+    i32 = [A.new_like(a, (cap,), np.int32) for _ in range(4)]
+    f64 = [A.new_like(a, (cap,), np.float64) for _ in range(3)]
+    pc, pl = A.new_like(a, (n,), np.int32), A.new_like(a, (n,), np.float64)
+    kt, k = np.zeros(1, np.int64), np.zeros(1, np.int64)
+    A.check(A.lib().hdb_flat_cluster_tree(_flat_handle(a, ctx), a.p, b.p, ww.p, ww.obj.shape[0], n, minClSize, cap,
+                                          A.ptr(kt), A.ptr(i32[0]), A.ptr(f64[0]), A.ptr(f64[1]), A.ptr(f64[2]),
+                                          A.ptr(i32[1]), A.ptr(i32[2]), A.ptr(i32[3]), A.ptr(pc), A.ptr(pl), A.ptr(k)),
+            "cluster_tree")
+    K = int(kt[0])
+    return ClusterTree(i32[0][:K], f64[0][:K], f64[1][:K], f64[2][:K], i32[1][:K], i32[2][:K], i32[3][:K], pc, pl,
+                       int(k[0]))
+
+
+def labels_at_levels(tree: ClusterTree, levels, ctx=None):
+    """Hierarchy rows at arbitrary levels (hdb_labels_at_levels): an (L, n) int32 array whose row
+    l holds the tree labels while every edge of weight <= levels[l] is still present (0 = noise).
+    Levels in any order, duplicates and +-inf allowed; NaN raises.  The tree's arrays and the
+    levels may each be host or device memory; the result lives where the tree's points do."""
+    par, bi = A.Arr(tree.parent, np.int32), A.Arr(tree.birth, np.float64)
+    pc, pl = A.Arr(tree.point_cluster, np.int32), A.Arr(tree.point_level, np.float64)
+    lv = A.Arr(levels if A.is_torch(levels) else np.atleast_1d(np.asarray(levels, dtype=np.float64)), np.float64)
+    L, n, K = int(lv.obj.shape[0]), int(pc.obj.shape[0]), int(par.obj.shape[0])
+    out = A.new_like(pc, (L, n), np.int32)
+    h = ctx.h if ctx is not None else None
+    if h is None:
+        for x in (pc, par, lv):
+            if x.device is not None and x.device.type == "cuda":
+                h = A.Context.get(x.device.index or 0).h
+                break
+    A.check(A.lib().hdb_labels_at_levels(h, par.p, bi.p, K, pc.p, pl.p, n, lv.p, L, A.ptr(out)), "labels_at_levels")
+    return out

@@ -421,6 +421,60 @@ int hdb_flat_outlier_scores(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, 
                             int64_t n, int32_t min_cl_size, double *scores, double *noise_level, int32_t *labels,
                             int64_t *n_clusters);
 
+/* The condensed cluster tree of the same hierarchy (HDBSCANStar.computeHierarchyAndClusterTree
+ * :208-474): what hdb_flat_labels builds and discards.  Inputs, tie rules, pointer rules (device,
+ * host or mixed; ctx may be NULL when every pointer is host memory) and status codes are exactly
+ * those of hdb_flat_labels; non-finite weights are out of scope, as for the scores.
+ *   K >= 1 clusters (0 only for n == 0) with 1-based TREE LABELS; 0 = noise / no parent.  Label 1
+ *   is the root (all points); labels 2..K order the other clusters by (birth level descending,
+ *   smallest member id ascending), so a parent's label is below its children's.  Entry i of a
+ *   per-cluster array describes tree label i + 1:
+ *     parent      tree label of the parent, 0 for the root
+ *     birth       the level at which the cluster appears (its parent's split); NaN for the root
+ *     death       the level at which its last points leave: its children's birth level when it
+ *                 splits, else the level of the last node on its chain
+ *     stability   the value FOSC compares: sum over its levels, descending, of
+ *                 count * (1/eps - 1/birth); NaN for the root (n >= 2), 0 for n == 1
+ *     size        points at birth;  min_id  smallest member id at birth
+ *     flat_label  1..n_clusters (the numbering of hdb_flat_labels) when FOSC selected the
+ *                 cluster, else 0 -- also 0 for a cluster below a selected one, and for the root
+ *   per point x:
+ *     point_cluster  tree label of last(x), the cluster x leaves as noise from
+ *     point_level    eps(x), bit-identical to hdb_flat_outlier_scores' noise_level; 0 for n == 1
+ *   The flat label of x is flat_label of the nearest selected cluster on the path from last(x)
+ *   to the root; the GLOSH eps_max is the subtree minimum of death.
+ * cap: entries available in each per-cluster array; hdb_cluster_tree_bound gives a value that
+ * always suffices.  *n_tree (required, host) receives K.  cap < K: HDB_EINVAL, *n_tree is still
+ * set to K, the message names both numbers and no array has been written.  Every per-cluster and
+ * per-point output, and n_clusters (host), may be NULL on its own.  n == 1: K = 1,
+ * point_cluster 1, point_level 0, death 0.  n < min_cl_size: K = 1 and every point leaves the
+ * root at the heaviest weight.  Synchronises (K returns to the host). */
+int hdb_flat_cluster_tree(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, const double *w, int64_t ne,
+                          int64_t n, int32_t min_cl_size, int64_t cap, int64_t *n_tree, int32_t *parent,
+                          double *birth, double *death, double *stability, int32_t *size, int32_t *min_id,
+                          int32_t *flat_label, int32_t *point_cluster, double *point_level, int64_t *n_clusters);
+
+/* Upper bound of K for n points: max(1, 2 * floor(n / min_cl_size) - 1) (leaf clusters are
+ * disjoint with >= min_cl_size points each, every split has >= 2 children); 0 for n <= 0.
+ * Host only, no context. */
+int64_t hdb_cluster_tree_bound(int64_t n, int32_t min_cl_size);
+
+/* Hierarchy rows at arbitrary levels (the DBSCAN*-style partitions; HDBSCANStar.java:393-414)
+ * from the arrays of hdb_flat_cluster_tree.  labels_out is L x n, row-major: row l holds the tree
+ * labels while every edge of weight <= levels[l] is still present:
+ *   0 when levels[l] < point_level[x]; otherwise start at C = point_cluster[x] and move to
+ *   parent[C] while birth[C] <= levels[l] (the root's NaN birth stops the walk).
+ * So a cluster's points carry the parent's label AT its birth level, a point is still in its
+ * cluster AT its own level, any level >= the heaviest weight (+inf too) gives all 1 and any level
+ * below every point level gives all 0.  Levels may come in any order, repeat, and be +-inf; a
+ * NaN level is HDB_EINVAL.  L == 0 or n == 0 is HDB_OK.  Pointer rules as hdb_flat_labels.  The
+ * tree is validated, never trusted: point_cluster outside 1..K, parent[i] outside 0..i, or
+ * parent[0] != 0 give HDB_EINVAL (no out-of-bounds read on host or device).  The device kernel
+ * climbs by binary lifting, O(log K) per (point, level).  Synchronises. */
+int hdb_labels_at_levels(hdb_ctx *ctx, const int32_t *parent, const double *birth, int64_t K,
+                         const int32_t *point_cluster, const double *point_level, int64_t n,
+                         const double *levels, int32_t L, int32_t *labels_out);
+
 /* -------------------------------------------------- record formats (§8(f) #3)
  * Host-only (no context, no device); see csrc/formats.cpp. */
 
