@@ -13,10 +13,11 @@ from .databubbles import (CombineStep, FirstStep, HdbscanDataBubbles, LocalModel
                           bubble_stats, merge_sorted_runs, nearest_sample, sort_edges_desc)
 from .driver import MRHDBSCANStar
 from .formats import (MapperDataset_github, double_to_string, format_cluster_tree, format_hierarchy,
-                      format_local_mst, format_outlier_scores, hierarchy_levels, parse_local_mst, read_dataset)
+                      format_local_mst, format_outlier_scores, hierarchy_levels, parse_constraints, parse_local_mst, read_dataset)
 from .hdbscanstar import (CosineSimilarity, DistanceCalculator, EuclideanDistance, HDBSCANStar,
                           ManhattanDistance, PearsonCorrelation, SupremumDistance, UndirectedGraph,
-                          ClusterTree, cluster_tree, cluster_tree_bound, distance_rows, flat_labels,
+                          ClusterTree, ConstrainedLabels, cluster_tree, cluster_tree_bound,
+                          constrained_flat_labels, distance_rows, flat_labels,
                           labels_at_levels, outlier_ranking, outlier_scores)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

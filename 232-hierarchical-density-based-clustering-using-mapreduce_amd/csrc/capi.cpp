@@ -639,4 +639,42 @@ int hdb_labels_at_levels(hdb_ctx *ctx, const int32_t *parent, const double *birt
     });
 }
 
+int hdb_constrained_flat_labels(hdb_ctx *ctx, const int32_t *parent, const double *stability, const int32_t *min_id,
+                                int64_t K, const int32_t *point_cluster, int64_t n, const int32_t *ca,
+                                const int32_t *cb, const int32_t *ctype, int64_t m, int32_t *num_sat,
+                                int32_t *prop_sat, double *prop_stability, int32_t *flat_label, int32_t *labels,
+                                int64_t *n_clusters) {
+    // the host path makes these checks itself; here they come before any array is staged
+    auto precheck = [&] {
+        if (m > HDB_MAX_CONSTRAINTS) HDB_THROW(HDB_EINVAL, "constrained flat labels: m exceeds 2^30 - 1 constraints");
+        if (K < 0 || n < 0 || m < 0 || (K > 0 && (!parent || !stability || !min_id)) || (n > 0 && !point_cluster) ||
+            (m > 0 && (!ca || !cb || !ctype)))
+            HDB_THROW(HDB_EINVAL, "bad arguments");
+    };
+    if (!ctx) {  // host-only use (all pointers in host memory): no device needed
+        try {
+            const ConstrainedOut o{num_sat, prop_sat, prop_stability, flat_label, labels, n_clusters};
+            return constrained_flat_labels_host(parent, stability, min_id, K, point_cluster, n, ca, cb, ctype, m, o);
+        } catch (const Error &e) {
+            set_error(e.msg);
+            return e.code;
+        } catch (const std::bad_alloc &) {
+            set_error("host allocation failed");
+            return HDB_ENOMEM;
+        }
+    }
+    return guarded(ctx, [&] {
+        precheck();
+        Stager sg(ctx);
+        const size_t nk = (size_t)K, np = (size_t)n, nm = (size_t)m;
+        const int32_t *dp = sg.in(parent, nk), *dmin = sg.in(min_id, nk), *dpc = sg.in(point_cluster, np);
+        const double *dst = sg.in(stability, nk);
+        const int32_t *da = sg.in(ca, nm), *db = sg.in(cb, nm), *dt = sg.in(ctype, nm);
+        const ConstrainedOut o{sg.out(num_sat, nk),    sg.out(prop_sat, nk), sg.out(prop_stability, nk),
+                               sg.out(flat_label, nk), sg.out(labels, np),   n_clusters};
+        constrained_flat_labels_device(ctx, dp, dst, dmin, K, dpc, n, da, db, dt, m, o);
+        sg.finish();
+    });
+}
+
 }  // extern "C"

@@ -102,6 +102,26 @@ void flat_cluster_tree_device(hdb_ctx *ctx, const int32_t *va, const int32_t *vb
 void labels_at_levels_device(hdb_ctx *ctx, const int32_t *parent, const double *birth, int64_t K,
                              const int32_t *point_cluster, const double *point_level, int64_t n,
                              const double *levels, int32_t L, int32_t *labels_out);
+// outputs of hdb_constrained_flat_labels: K entries per cluster array (entry i = tree label
+// i + 1), n labels, each nullable; n_clusters is a host scalar
+struct ConstrainedOut {
+    int32_t *num_sat, *prop_sat;
+    double *prop_stability;
+    int32_t *flat_label;
+    int32_t *labels;
+    int64_t *n_clusters;
+};
+constexpr int64_t HDB_MAX_CONSTRAINTS = (int64_t(1) << 30) - 1;  // counts reach 2m and are Java ints
+// constraint-aware flat extraction over a cluster tree, all arrays on the device (constraints.hip);
+// synchronises
+void constrained_flat_labels_device(hdb_ctx *ctx, const int32_t *parent, const double *stability,
+                                    const int32_t *min_id, int64_t K, const int32_t *point_cluster, int64_t n,
+                                    const int32_t *ca, const int32_t *cb, const int32_t *ctype, int64_t m,
+                                    const ConstrainedOut &o);
+// the same on host arrays (constraints.cpp)
+int constrained_flat_labels_host(const int32_t *parent, const double *stability, const int32_t *min_id, int64_t K,
+                                 const int32_t *point_cluster, int64_t n, const int32_t *ca, const int32_t *cb,
+                                 const int32_t *ctype, int64_t m, const ConstrainedOut &o);
 // K <= max(1, 2 floor(n / mcs) - 1): disjoint leaves of >= mcs points, every split >= 2 ways
 inline int64_t cluster_tree_bound(int64_t n, int32_t mcs) {
     if (n <= 0) return 0;

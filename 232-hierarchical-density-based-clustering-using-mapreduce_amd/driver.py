@@ -73,7 +73,8 @@ class MRHDBSCANStar:
                  seed=20210101, distanceFunction=None, all_inter_edges=True, max_levels=64, ctx=None,
                  device=0, flat_labels=True, profile=False, exact_prim_leaves=False, group=None,
                  prim_leaf_max=LEAF_PRIM_MAX, model_threads=4, defer_leaves=True, bubble_slices=BUBBLE_SLICES,
-                 emulate_ranks=(), cores_first=False, outlier_scores=False, cluster_tree=False):
+                 emulate_ranks=(), cores_first=False, outlier_scores=False, cluster_tree=False,
+                 constraints=None):
         self.minPts = minPts
         self.minClSize = minClSize
         self.processing_units = processing_units
@@ -93,6 +94,12 @@ class MRHDBSCANStar:
         # outlier_scores needs.  One hierarchy call: the labels (and the scores, when asked for)
         # are then re-derived from the tree, not from a second K6 pass
         self.cluster_tree = cluster_tree
+        # (ca, cb, ctype) must-link / cannot-link pairs (formats.parse_constraints): the
+        # semi-supervised extraction of hdb_constrained_flat_labels as out["constrained"], beside
+        # the unconstrained labels; needs cluster_tree
+        if constraints is not None and not cluster_tree:
+            raise ValueError("constraints need cluster_tree=True")
+        self.constraints = None if constraints is None else tuple(constraints)
         self.profile = profile       # phase wall times (synchronising) in self.timings
         # True: every leaf, however large, runs the reference Prim (the exact edge list of
         # HDBSCANStar.constructMST, ties included; stepwise above 65,536 points).  False:
@@ -520,6 +527,9 @@ class MRHDBSCANStar:
                 if self.outlier_scores:
                     out["outlier_scores"] = tree.outlier_scores()
                     out["noise_levels"] = tree.point_level
+                if self.constraints is not None:
+                    from .hdbscanstar import constrained_flat_labels
+                    out["constrained"] = constrained_flat_labels(tree, *self.constraints, ctx=c)
             elif self.outlier_scores:
                 scores = torch.empty(n, dtype=torch.float64, device=dev)
                 noise = torch.empty(n, dtype=torch.float64, device=dev)

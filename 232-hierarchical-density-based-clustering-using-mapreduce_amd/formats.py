@@ -152,19 +152,52 @@ def format_hierarchy(tree, levels=None, compact: bool = True, ctx=None):
     return "".join(parts), offsets
 
 
-def format_cluster_tree(tree, offsets=None) -> str:
+def format_cluster_tree(tree, offsets=None, constrained=None) -> str:
     """The cluster-tree file's text (HDBSCANStar.java:449-468): one line
     ``label,birth,death,stability,0,0,offset,parentLabel\\n`` per cluster in label order (the two
     zeros are the constraint counts of a run without constraints); doubles as ``Double.toString``
     writes them (``NaN`` for the root's birth and stability).  ``offsets``: the second result of
-    format_hierarchy (default: zeros)."""
+    format_hierarchy (default: zeros).  ``constrained``: the record of constrained_flat_labels; the
+    two columns are then ``0.5 * num_sat / m`` and ``0.5 * prop_sat / m`` as doubles (``NaN`` for
+    m == 0, Java's 0.0 / 0)."""
     t = tree.host()
     off = np.zeros(t.n_tree, dtype=np.int64) if offsets is None else np.asarray(offsets, dtype=np.int64)
     if off.shape[0] != t.n_tree:
         raise ValueError("offsets must have one entry per cluster")
     d = double_to_string
-    return "".join(f"{i + 1},{d(t.birth[i])},{d(t.death[i])},{d(t.stability[i])},0,0,{int(off[i])},{int(t.parent[i])}\n"
+    if constrained is None:
+        cols = ["0,0"] * t.n_tree
+    else:
+        host = lambda x: np.asarray(x.detach().cpu().numpy() if hasattr(x, "detach") else x, dtype=np.float64)
+        num, prop = host(constrained.num_sat), host(constrained.prop_sat)
+        if num.shape[0] != t.n_tree or prop.shape[0] != t.n_tree:
+            raise ValueError("constrained must have one entry per cluster")
+        with np.errstate(invalid="ignore", divide="ignore"):
+            m = np.float64(constrained.m)
+            cols = [f"{d(0.5 * a / m)},{d(0.5 * b / m)}" for a, b in zip(num, prop)]
+    return "".join(f"{i + 1},{d(t.birth[i])},{d(t.death[i])},{d(t.stability[i])},{cols[i]},{int(off[i])},{int(t.parent[i])}\n"
                    for i in range(t.n_tree))
+
+
+def parse_constraints(text):
+    """The constraints file (Main.java:49 ``constraints=<file>``): one constraint per line,
+    ``a,b,ml`` (must-link) or ``a,b,cl`` (cannot-link), a and b point ids.  Returns
+    ``(ca, cb, ctype)`` as int32 arrays (ctype 0 = must-link, 1 = cannot-link).  A trailing
+    newline is allowed; anything else -- a blank line, another field count, a negative or
+    non-decimal id, another type -- raises ValueError naming the line."""
+    if isinstance(text, (bytes, bytearray)):
+        text = bytes(text).decode()
+    lines = text.split("\n")
+    if lines and lines[-1] == "":
+        lines.pop()
+    ca, cb, ct = [], [], []
+    for no, line in enumerate(lines, 1):
+        f = line.rstrip("\r").split(",")
+        if len(f) != 3 or f[2] not in ("ml", "cl") or not (f[0].isascii() and f[0].isdigit()) \
+                or not (f[1].isascii() and f[1].isdigit()) or int(f[0]) > 2 ** 31 - 1 or int(f[1]) > 2 ** 31 - 1:
+            raise ValueError(f"constraints line {no}: expected 'a,b,ml' or 'a,b,cl', got {line!r}")
+        ca.append(int(f[0])), cb.append(int(f[1])), ct.append(0 if f[2] == "ml" else 1)
+    return np.array(ca, np.int32), np.array(cb, np.int32), np.array(ct, np.int32)
 
 
 def parse_local_mst(text):

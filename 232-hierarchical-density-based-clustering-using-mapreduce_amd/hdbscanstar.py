@@ -409,3 +409,53 @@ def labels_at_levels(tree: ClusterTree, levels, ctx=None):
                 break
     A.check(A.lib().hdb_labels_at_levels(h, par.p, bi.p, K, pc.p, pl.p, n, lv.p, L, A.ptr(out)), "labels_at_levels")
     return out
+
+
+MUST_LINK, CANNOT_LINK = 0, 1  # HDB_CONSTRAINT_*
+
+
+class ConstrainedLabels:
+    """The result of constrained_flat_labels: ``labels`` (n; 1..n_clusters, 0 = noise),
+    ``n_clusters``, and per cluster (entry i = tree label i + 1) ``flat_label``, ``num_sat``
+    (numConstraintsSatisfied), ``prop_sat`` and ``prop_stability`` (the propagated values);
+    ``m`` constraints, ``satisfied_fraction`` = 0.5 * prop_sat[root] / m as the reference prints
+    it (NaN for m == 0, Java's 0.0 / 0)."""
+
+    def __init__(self, labels, n_clusters, flat_label, num_sat, prop_sat, prop_stability, m):
+        self.labels, self.n_clusters, self.flat_label = labels, int(n_clusters), flat_label
+        self.num_sat, self.prop_sat, self.prop_stability, self.m = num_sat, prop_sat, prop_stability, int(m)
+
+    @property
+    def satisfied_fraction(self) -> float:
+        if self.m == 0 or self.prop_sat.shape[0] == 0:
+            return float("nan")
+        return 0.5 * int(self.prop_sat[0]) / self.m
+
+
+def constrained_flat_labels(tree: ClusterTree, ca, cb, ctype, ctx=None) -> ConstrainedLabels:
+    """Semi-supervised flat extraction (hdb_constrained_flat_labels; DESIGN.md "Constrained flat
+    labels"): the FOSC selection of the tree under must-link (ctype 0) and cannot-link (ctype 1)
+    pairs of point ids -- a cluster that satisfies more constraints than its descendants is kept,
+    stability breaks ties.  Without constraints the result equals tree.flat_label /
+    tree.flat_labels().  The tree's arrays and the constraints may each be host or device memory;
+    tensors in give tensors out (the results live where the tree's arrays do)."""
+    par, st, mi = A.Arr(tree.parent, np.int32), A.Arr(tree.stability, np.float64), A.Arr(tree.min_id, np.int32)
+    pc = A.Arr(tree.point_cluster, np.int32)
+    a, b, t = A.Arr(ca, np.int32), A.Arr(cb, np.int32), A.Arr(ctype, np.int32)
+    K, n, m = int(par.obj.shape[0]), int(pc.obj.shape[0]), int(a.obj.shape[0])
+    if b.obj.shape[0] != m or t.obj.shape[0] != m:
+        raise ValueError("ca, cb and ctype must have one entry per constraint")
+    num, prop, flat = (A.new_like(par, (K,), np.int32) for _ in range(3))
+    pst = A.new_like(par, (K,), np.float64)
+    labels = A.new_like(pc, (n,), np.int32)
+    k = np.zeros(1, np.int64)
+    h = ctx.h if ctx is not None else None
+    if h is None:
+        for x in (pc, par, st, mi, a, b, t):
+            if x.device is not None and x.device.type == "cuda":
+                h = A.Context.get(x.device.index or 0).h
+                break
+    A.check(A.lib().hdb_constrained_flat_labels(h, par.p, st.p, mi.p, K, pc.p, n, a.p, b.p, t.p, m, A.ptr(num),
+                                                A.ptr(prop), A.ptr(pst), A.ptr(flat), A.ptr(labels), A.ptr(k)),
+            "constrained_flat_labels")
+    return ConstrainedLabels(labels, int(k[0]), flat, num, prop, pst, m)

@@ -475,6 +475,44 @@ int hdb_labels_at_levels(hdb_ctx *ctx, const int32_t *parent, const double *birt
                          const int32_t *point_cluster, const double *point_level, int64_t n,
                          const double *levels, int32_t L, int32_t *labels_out);
 
+/* Semi-supervised flat extraction (Main.java:49,434-436 "constraints=<file>"; Constraint.java,
+ * HDBSCANStar.calculateNumConstraintsSatisfied :738-789, the constraint branches of
+ * Cluster.propagate :98-142, findProminentClusters) from the arrays of hdb_flat_cluster_tree:
+ * parent / stability / min_id (K each) and point_cluster (n), in tree labels.  m constraints:
+ * ca[k], cb[k] are point ids, ctype[k] one of the two values below.
+ *   last(x) = point_cluster[x]; anc(C) = C and its ancestors; L = LCA(last(a), last(b)).
+ *   num_sat[C]  (numConstraintsSatisfied): a must-link pair adds 2 to every C in anc(L), the root
+ *     included, a == b too; a cannot-link pair adds 1 to every C from last(a) up to but excluding
+ *     L, and the same for b (nothing when last(a) == last(b); never to the root).
+ *   virt[C]: for a cluster with children, the cannot-link endpoints x with last(x) == C (both
+ *     endpoints, a == b too); 0 for a leaf.
+ *   Children before parents, a node's children in ASCENDING TREE LABEL:
+ *     prop_sat[C] = virt[C] + sum of chosen_sat(child); prop_stability[C] = 0.0 + the children's
+ *     chosen_stab, one IEEE addition per child in that order; both 0 for a leaf.
+ *     A non-root C is chosen as itself when it is a leaf, or num_sat > prop_sat, or
+ *     num_sat == prop_sat && stability >= prop_stability (a NaN stability loses); then
+ *     chosen = (num_sat, stability), else chosen = (prop_sat, prop_stability).  The root is never
+ *     chosen; 0.5 * prop_sat[root] / m is the satisfied fraction the reference prints.
+ *   The selected clusters are the topmost self-chosen ones below the root on each chain;
+ *   flat_label numbers them 1..n_clusters by ascending (min_id, tree label), 0 for every other
+ *   cluster; labels[x] = flat_label of the nearest selected cluster in anc(last(x)), else 0.
+ *   With m == 0 flat_label and labels are exactly those of hdb_flat_cluster_tree / hdb_flat_labels.
+ * Outputs: num_sat, prop_sat, prop_stability, flat_label (K each), labels (n), n_clusters (host);
+ * each may be NULL on its own.  Counts are int32 (Java int): m > 2^30 - 1 is HDB_EINVAL, checked
+ * before any array is read.  The input is validated, never trusted: parent[0] != 0, parent[i]
+ * outside 0..i (a further cluster with parent 0 is a root of its own: never chosen), point_cluster outside 1..K, a point id outside 0..n-1 or a type other than 0 / 1
+ * give HDB_EINVAL with a message naming the field (no out-of-bounds access on host or device; the
+ * outputs are then undefined).  K == 1: n_clusters 0, every label 0, num_sat[0] = 2 * the
+ * must-link count.  K == 0 (the tree of n == 0): HDB_OK.  Pointer rules as hdb_labels_at_levels
+ * (host, device or mixed; ctx may be NULL when every pointer is host memory).  Synchronises. */
+#define HDB_CONSTRAINT_MUST_LINK 0
+#define HDB_CONSTRAINT_CANNOT_LINK 1
+int hdb_constrained_flat_labels(hdb_ctx *ctx, const int32_t *parent, const double *stability, const int32_t *min_id,
+                                int64_t K, const int32_t *point_cluster, int64_t n, const int32_t *ca,
+                                const int32_t *cb, const int32_t *ctype, int64_t m, int32_t *num_sat,
+                                int32_t *prop_sat, double *prop_stability, int32_t *flat_label, int32_t *labels,
+                                int64_t *n_clusters);
+
 /* -------------------------------------------------- record formats (§8(f) #3)
  * Host-only (no context, no device); see csrc/formats.cpp. */
 
