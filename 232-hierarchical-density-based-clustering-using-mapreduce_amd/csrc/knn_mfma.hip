@@ -21,6 +21,46 @@
 // skipped only when approx - bound > T, T = the query's current KC-th smallest exact value:
 // its exact value is then > T and could not enter the list.
 //
+// Range.  The scale sc = 2^-e, 2^(e-1) <= M < 2^e for M = max |x| + |mu| >= max |x - mu|, is
+// an exact power of two, and every quantity of the screen lives in the scaled domain, where
+// |v| < 1.  Only the two-pass kernel converts between the domains, by a factor sc^2.  The 1e-30
+// of the bound is almost all slack: what FP32 and bf16 underflow can drop is below 1e-34 (768
+// products, each off by less than 2^-126).  Three regimes lie outside the comfortable one:
+//  - M < 2^-456 (SC_EXP_MAX): the ideal scale would leave the range where the argument above
+//    holds -- sc^2 is +inf from M < 2^-512 on (thresholds times it and bounds over it turn into
+//    inf, 0 or NaN), sc itself from M < 2^-1024 on (every v is +-inf or NaN, nothing is logged
+//    and every list entry would be Double.MAX_VALUE) -- and below M ~ 2^-484 the exact values are
+//    so close to the subnormals that their own rounding (d 2^-1075 absolute, sc^2 times that
+//    in the scaled domain) outgrows the bound's absolute term.  centre_kernel therefore clamps
+//    the scale to 2^456: sc^2 <= 2^912 is finite, (approx + bound) / sc^2 >= 1e-32 2^-912 (the
+//    sum is at least the bound's slack) is a normal number, so the division by a power of
+//    two stays exact, and the rounding of an exact value is at most 256 * 2^-1075 * 2^912 =
+//    2^-155 in the scaled domain, far inside the 1e-30.
+//    A scale smaller than the ideal one only shrinks the v: every relative term of the bound is
+//    unchanged (x - mu is exact below 2^-1021, the product with sc has no rounding), the
+//    absolute term 1e-30 covers what FP32 and bf16 underflow drop, exactly as it does for rows
+//    far below M at the ideal scale.  The screen then rules out little or nothing (below
+//    M ~ 2^-506 every |v|^2 is under 1e-30): each candidate is logged, the logs overflow and
+//    the two-pass kernel re-computes every pair in FP64.
+//  - M >= 2^512: sc^2 is subnormal, and from M >= 2^537 (sc <= 2^-538) on it rounds to +0 while
+//    the squared distances of rows closer than 2^512 are still finite, with scaled values up
+//    to 2^-52: a threshold formed as thr * (sc * sc) is then 0 and every pair above the 1e-30
+//    floor would be skipped, true neighbours among them.  Nothing is clamped here (a larger
+//    scale than the ideal one would push the v past 1); instead no product sc * sc is ever
+//    formed.  The single pass never needs it.  The two-pass kernel changes domain in two steps,
+//    (thr * sc) * sc and ((approx + bound) / sc) / sc: sc is a power of two, so each step is
+//    exact unless it underflows or overflows.  An underflow moves the scaled threshold by at
+//    most 2^-1075 (2^-1075 sc <= 2^-619 when the first step underflows and sc > 1), against a
+//    skip margin of the bound's slack, above 9e-31; an overflow gives +inf, which
+//    as a pass-0 value is never below a threshold (a looser bound, never a wrong one) and as a
+//    threshold skips nothing.  Exact values that overflow to +inf are not below
+//    Double.MAX_VALUE and enter no list, as in the FP64 scan.
+//  - rows far below M (unit rows beside 1e200): their v, norms and products underflow to 0 in
+//    FP32/bf16 or already in FP64; approx is then within the 1e-30 of 0 for every pair among
+//    them, nothing is ruled out, and the log overflow sends the call to the two-pass kernel.
+// A sum, a maximum or M that is not finite (NaN or infinite input, column sums that overflow)
+// declines the call: the FP64 scan answers.
+//
 // Work decomposition: a workgroup owns 128 queries (their bf16 fragments stay in VGPRs) and
 // streams all candidates in blocks of 64 through LDS; its 8 waves each produce one 32 x 32
 // tile of the 128 x 64 block.  Pairs that pass the screen are re-checked by the lane holding
@@ -47,6 +87,7 @@ constexpr int MQ = 128;  // queries per workgroup (8 waves: 4 query rows x 2 can
 constexpr int NT = 512;  // threads per workgroup
 constexpr int MC = 64;  // candidates per streamed block
 constexpr int KS = 16;  // k per MFMA step
+constexpr int SC_EXP_MAX = 456;  // largest exponent of the scale (header: "Range")
 
 // ---------------------------------------------------------------- prep
 // per-column partial sums (centre) and max |x| over row slices; coalesced: consecutive
@@ -93,8 +134,9 @@ __global__ void centre_kernel(const double *__restrict__ part_sum, const double 
         const double M = smax[0];
         int e = 0;
         if (isfinite(M) && M > 0) frexp(M, &e);
+        if (e < -SC_EXP_MAX) e = -SC_EXP_MAX;  // M < 2^-456: a smaller scale than ideal (header: "Range")
         prm[0] = isfinite(M) ? 1.0 : 0.0;  // usable
-        prm[1] = ldexp(1.0, -e);           // scale: exact power of two
+        prm[1] = ldexp(1.0, -e);           // scale: exact power of two, 2^-1024 .. 2^456
     }
 }
 
@@ -192,7 +234,9 @@ __global__ __launch_bounds__(NT) void knn_mfma_kernel(const double *__restrict__
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int wq = wave & 3, wc = wave >> 2;
     const int64_t qbase = (int64_t)blockIdx.x * MQ;
-    const double sc = prm[1], sc2 = sc * sc;
+    // sc * sc would round to +0 from sc = 2^-538 on: thresholds and bounds change domain in two
+    // exact steps (header: "Range")
+    const double sc = prm[1];
     const double eps_dot = 2.0 * (3.1 * 0x1p-16 + 3.0 * DP * 0x1p-24) * 1.01;
     const int ex = excl & 1;
 
@@ -215,7 +259,7 @@ __global__ __launch_bounds__(NT) void knn_mfma_kernel(const double *__restrict__
         qn_s[tid] = nrm[qbase + tid];
         const double t0 = (PASS == 1 && thr_init) ? thr_init[qbase + tid] : INFINITY;
         thr_s[tid] = t0;
-        thrf_s[tid] = (float)(t0 * sc2) * (1.0f + 1e-6f) + 1e-30f;  // rounded up (FP32 pre-screen)
+        thrf_s[tid] = (float)((t0 * sc) * sc) * (1.0f + 1e-6f) + 1e-30f;  // rounded up (FP32 pre-screen)
         cnt_s[tid] = 0;
     }
     unsigned long long n_re = 0;
@@ -289,11 +333,11 @@ __global__ __launch_bounds__(NT) void knn_mfma_kernel(const double *__restrict__
             const double bound = eps_dot * qn_s[qr] * cn + 4e-13 * (q2 + c2) + 1e-30;
             double val;
             if (PASS == 0) {
-                val = (approx + bound) / sc2;  // rigorous upper bound of the exact value
+                val = ((approx + bound) / sc) / sc;  // rigorous upper bound of the exact value
                 if (!(val < thr_s[qr])) continue;
             } else {
-                if (approx - bound > thr_s[qr] * sc2) continue;
-                val = (excl & 2) ? approx / sc2 : exact_sq<DP>(X + qid * d, X + cid * d, d);
+                if (approx - bound > (thr_s[qr] * sc) * sc) continue;
+                val = (excl & 2) ? (approx / sc) / sc : exact_sq<DP>(X + qid * d, X + cid * d, d);
                 n_re++;
             }
             const int slot = atomicAdd(&cnt_s[qr], 1);
@@ -306,7 +350,7 @@ __global__ __launch_bounds__(NT) void knn_mfma_kernel(const double *__restrict__
             cnt_s[tid] = 0;
             const double t = top[KC - 1] < thr_s[tid] ? top[KC - 1] : thr_s[tid];
             thr_s[tid] = t;
-            thrf_s[tid] = (float)(t * sc2) * (1.0f + 1e-6f) + 1e-30f;
+            thrf_s[tid] = (float)((t * sc) * sc) * (1.0f + 1e-6f) + 1e-30f;
         }
         __syncthreads();
     }

@@ -158,7 +158,29 @@ int hdb_core_distances(hdb_ctx *ctx, const double *X, int64_t n, int32_t d, int3
                        int32_t semantics, double *core_out);
 
 /* Per-row k smallest distances, ascending (Double.MAX_VALUE padded), optional neighbour
- * indices.  The value lists are the kernel output every core semantics derives from. */
+ * indices.  The value lists are the kernel output every core semantics derives from.
+ * idx_out exists only for the euclidean metric with d in {1..6, 8, 16}: any other metric or
+ * dimension with a non-null idx_out is HDB_EINVAL.
+ *
+ * Degenerate and non-finite input at d > 16 (hdb_core_distances and hdb_knn; every path gives the
+ * reference's result, bit for bit: the strict '<' insertion into a Double.MAX_VALUE buffer,
+ * HDBSCANStar.java:79-97, over distances summed in dimension order):
+ *  - A pair whose distance is NaN (a NaN coordinate; inf - inf in one coordinate) or not below
+ *    Double.MAX_VALUE (an infinite coordinate, a squared distance that overflows) never enters
+ *    a list.  A row all of whose pairs are such keeps Double.MAX_VALUE in every entry, and so
+ *    does every entry past the number of candidates when fewer than k rows qualify (n - 1 < k
+ *    with excl_self, n < k without): the reference's padding, also as a core distance.
+ *  - With a NaN or infinite coordinate anywhere in X, or column sums that overflow, the matrix-
+ *    core path (euclidean, 16 < d <= 256, n >= "knn_mfma_min_n") declines before it runs a
+ *    kernel and the FP64 scan answers, as it does for d > 256 and for "knn_mfma" = 0.
+ *  - Squared distances that underflow are the reference's: +0.0 or the subnormal the sequential
+ *    sum rounds to, ties included.  Finite input whose column sums are finite stays on the
+ *    matrix-core path at any magnitude: its power-of-two scale is clamped where the ideal one
+ *    would leave the double range (max |x - mean| below 2^-456), the square of the scale is
+ *    never formed (it would round to 0 from max |x - mean| >= 2^537 on, where rows closer than
+ *    2^512 still have finite distances; csrc/knn_mfma.hip "Range"), and input it cannot
+ *    separate (identical rows, rows far below the largest) is re-computed pair by pair in
+ *    FP64. */
 int hdb_knn(hdb_ctx *ctx, const double *X, int64_t n, int32_t d, int32_t k, int32_t metric, int32_t excl_self,
             double *dist_out /* n*k */, int32_t *idx_out /* n*k, nullable */);
 

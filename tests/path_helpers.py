@@ -45,6 +45,13 @@ def bits_eq(a, b):
                                                      np.where(nb, 0.0, b).view(np.uint64))
 
 
+def k1m_launches(ctx):
+    """(screen or two-pass kernel launches, log re-check launches, k-means layouts) since the last
+    call, on a context with timing on: the single pass is (1, 1, .), the two-pass kernel alone
+    (1, 0, 0), a single pass whose log overflowed (2, 1, .)"""
+    return tuple(ctx.kernel_time(k, reset=True)[1] for k in ("knn_mfma", "knn_mfma_final", "knn_mfma_order"))
+
+
 @functools.lru_cache(maxsize=4)
 def _pairs(n):
     i, j = np.triu_indices(n, 1)

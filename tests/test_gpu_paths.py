@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from conftest import blobs, golden
-from path_helpers import MST_CASES, bits_eq, edge_set, mst_case, options, spanning_tree
+from path_helpers import MST_CASES, bits_eq, edge_set, k1m_launches, mst_case, options, spanning_tree
 from test_flat_labels import lib_flat
 from test_gpu_mfma import embeddings
 from test_gpu_parity import split_scan_case
@@ -35,13 +35,6 @@ def star(pkg, ctx):
 
 
 # ----------------------------------------------------------------------------------- K1m
-def k1m_launches(ctx):
-    """(screen or two-pass kernel launches, log re-check launches, k-means layouts) since the last
-    call: the single pass is (1, 1, .), the two-pass kernel alone (1, 0, 0), a single pass whose
-    log overflowed (2, 1, .)"""
-    return tuple(ctx.kernel_time(k, reset=True)[1] for k in ("knn_mfma", "knn_mfma_final", "knn_mfma_order"))
-
-
 @pytest.fixture()
 def timed(ctx):
     ctx.set_timing(True)
