@@ -8,6 +8,7 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "internal.hpp"
 
 namespace hdb {
 
@@ -267,6 +268,7 @@ int hdb_ctx_create(int device, hdb_ctx **out) {
         for (const char *k : {"prim_coop_plain_retries", "prim_coop_steps", "prim_coop_launches", "bubble_knn_replay_overflows",
                               "boruvka_visits_sum", "boruvka_evals_sum", "boruvka_bound_ns_sum", "boruvka_inf_edges"})
             c->stats[k] = 0;
+        boruvka_generic_stats_init(c);
         // per-kernel HIP-event timing from birth (contexts created on worker threads, bench.py)
         if (const char *e = getenv("HDB_KERNEL_TIMING")) c->timing = atoi(e) != 0;
         // A/B runs of unmodified programs: HDB_OPTS="name=value,name=value", every pair applied

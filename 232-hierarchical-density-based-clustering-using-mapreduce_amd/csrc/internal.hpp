@@ -66,6 +66,12 @@ void exact_leaf_device(hdb_ctx *ctx, const double *X, int64_t n, int d, int min_
                        double *core, int self_edges, int32_t *va, int32_t *vb, double *w);
 void boruvka_device(hdb_ctx *ctx, const double *X, int64_t n, int d, const double *core, int metric, int32_t *va,
                     int32_t *vb, double *w);
+// K2g (boruvka_generic.hip): the same contract for every metric and d by a tiled all-pairs FP64
+// scan; boruvka_device routes to it whatever K2b's index does not cover
+void boruvka_generic_device(hdb_ctx *ctx, const double *X, int64_t n, int d, const double *core, int metric,
+                            int32_t *va, int32_t *vb, double *w);
+// its tile constants and round count as stats (boruvka_gen_qt / _ct / _dc / _rounds)
+void boruvka_generic_stats_init(hdb_ctx *ctx);
 // K2b's infinite-weight tail on host arrays (inf_edges.cpp): X, core in id order; (ea, eb)[m] the
 // finite edges K2b found.  Writes the +inf edges that join their trees under (w, s, lo, hi) and
 // returns their count; rows_left / first_left: rows outside the largest tree that only NaN

@@ -2418,8 +2418,9 @@ void exact_leaf_device(hdb_ctx *ctx, const double *X, int64_t n, int d, int min_
 
 void boruvka_device(hdb_ctx *ctx, const double *X, int64_t n, int d, const double *core, int metric, int32_t *va,
                     int32_t *vb, double *w) {
-    if (metric != HDB_METRIC_EUCLIDEAN) HDB_THROW(HDB_EINVAL, "boruvka: euclidean metric only");
     if (n <= 1) return;
+    // K2b for the shapes its index exists for; every other metric and d: K2g (boruvka_generic.hip)
+    if (metric != HDB_METRIC_EUCLIDEAN) return boruvka_generic_device(ctx, X, n, d, core, metric, va, vb, w);
     switch (d) {
     case 1: boruvka_impl<1>(ctx, X, n, core, va, vb, w); break;
     case 2: boruvka_impl<2>(ctx, X, n, core, va, vb, w); break;
@@ -2427,7 +2428,7 @@ void boruvka_device(hdb_ctx *ctx, const double *X, int64_t n, int d, const doubl
     case 4: boruvka_impl<4>(ctx, X, n, core, va, vb, w); break;
     case 8: boruvka_impl<8>(ctx, X, n, core, va, vb, w); break;
     case 16: boruvka_impl<16>(ctx, X, n, core, va, vb, w); break;
-    default: HDB_THROW(HDB_EINVAL, "boruvka: d must be one of 1,2,3,4,8,16");
+    default: boruvka_generic_device(ctx, X, n, d, core, metric, va, vb, w); break;
     }
 }
 

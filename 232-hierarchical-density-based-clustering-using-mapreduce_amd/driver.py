@@ -13,9 +13,9 @@ oracle for the parity tests):
   leaves  (FirstStep.java:104-120)  subsets <= processing_units (or forced, D9): cumulative
           core distances + Prim with self edges over the rows in ascending global id, one
           batched call for all leaves <= LEAF_PRIM_MAX points (and for any size when
-          exact_prim_leaves is set or K2b does not apply: other metrics, other d); larger
-          forced leaves use hdb_exact_mst: the same cores + Boruvka on one index (exact
-          weights; topology differs from Prim only on ties).  Leaves are end points of
+          exact_prim_leaves is set or K2b does not apply: other metrics, other d -- unless
+          boruvka_any_leaves routes those to K2g); larger forced leaves use hdb_exact_mst:
+          the same cores + Boruvka (exact weights; topology differs from Prim only on ties).  Leaves are end points of
           the subset tree, so they are deferred (defer_leaves): every level's leaves run as
           one batch after the level loop (identical blocks, placed by their canonical ids)
   big subsets: D2 samples -> keyed nearest sample (FirstStep.java:74-85, D3) -> bulk
@@ -52,9 +52,15 @@ BORUVKA_DIMS = (1, 2, 3, 4, 8, 16)  # d with a K1t/K2b instantiation (csrc/spati
 BUBBLE_SLICES = 8  # D11: CombineStep partials per fixed row slice (a rank folds only its slices)
 
 
-def boruvka_ok(metric: int, d: int, min_pts: int) -> bool:
-    """hdb_exact_mst's K2b path: Euclidean, d with an instantiation, 2 <= minPts <= 32."""
-    return metric == A.METRIC["euclidean"] and d in BORUVKA_DIMS and 2 <= min_pts <= 32
+def boruvka_ok(metric: int, d: int, min_pts: int, any_shape: bool = False) -> bool:
+    """whether a forced leaf above LEAF_PRIM_MAX goes to hdb_exact_mst.  The call itself accepts
+    every metric and d; by default the driver sends it only K2b's shapes (Euclidean, d with an
+    instantiation), so the topology of every other run stays the reference Prim's.  any_shape
+    (boruvka_any_leaves): every metric and d, K2g's tiled scan where K2b has no index.
+    Either way 2 <= minPts <= 32."""
+    if not 2 <= min_pts <= 32:
+        return False
+    return any_shape or (metric == A.METRIC["euclidean"] and d in BORUVKA_DIMS)
 
 
 def sample_ids(n_key: int, k: float, samples_per_subset, seed: int, iteration: int, key: int):
@@ -74,7 +80,7 @@ class MRHDBSCANStar:
                  device=0, flat_labels=True, profile=False, exact_prim_leaves=False, group=None,
                  prim_leaf_max=LEAF_PRIM_MAX, model_threads=4, defer_leaves=True, bubble_slices=BUBBLE_SLICES,
                  emulate_ranks=(), cores_first=False, outlier_scores=False, cluster_tree=False,
-                 constraints=None):
+                 constraints=None, boruvka_any_leaves=False):
         self.minPts = minPts
         self.minClSize = minClSize
         self.processing_units = processing_units
@@ -109,6 +115,10 @@ class MRHDBSCANStar:
         # leaves up to this size run the reference Prim (exact topology, latency-bound: one
         # step per point); larger ones K2b where it applies (exact weights, ties may differ)
         self.prim_leaf_max = prim_leaf_max
+        # True: forced leaves above prim_leaf_max use hdb_exact_mst for every metric and d (K2g
+        # where K2b has no index) instead of the stepwise Prim; off by default, so the edge
+        # topology of existing runs does not change
+        self.boruvka_any_leaves = boruvka_any_leaves
         # a level's local models run concurrently, one host thread (own context and stream)
         # each: a bubble Prim occupies only ceil(b / 1024) CUs
         self.model_threads = int(os.environ.get("HDB_MODEL_THREADS", model_threads))
@@ -188,7 +198,7 @@ class MRHDBSCANStar:
         c = self._c()
         d = X.shape[1]
         prim = lambda n: (n <= self.prim_leaf_max or self.exact_prim_leaves
-                          or not boruvka_ok(self.metric, d, self.minPts))
+                          or not boruvka_ok(self.metric, d, self.minPts, self.boruvka_any_leaves))
         small = [(k, r) for k, r in zip(keys, rows_list) if prim(r.shape[0])]
         if small:
             rows = torch.cat([r for _, r in small])

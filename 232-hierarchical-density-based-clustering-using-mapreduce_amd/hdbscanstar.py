@@ -184,8 +184,11 @@ class HDBSCANStar:
         return va, vb, w, f1, f2, nd
 
     def constructMSTBoruvka(self, dataSet, coreDistances, selfEdges: bool, distanceFunction=None) -> UndirectedGraph:
-        """Large-graph MST (K2b): same sorted weights as constructMST, ties broken by
-        (w, min id, max id); edges sorted by that key, then the self edges."""
+        """Large-graph MST: same sorted weights as constructMST, the unique tree under the strict
+        edge order (w, s, min id, max id) of include/hdbmi.h; edges sorted by (w, min id, max id),
+        then the self edges.  Every distanceFunction and every d: K2b's index for Euclidean
+        d in {1, 2, 3, 4, 8, 16}, K2g's tiled all-pairs scan for everything else (cosine and
+        Pearson weights can be a few ulps below zero and come back as computed)."""
         X = A.Arr(dataSet, np.float64)
         n, d = X.obj.shape
         core = A.Arr(coreDistances, np.float64)
@@ -202,7 +205,8 @@ class HDBSCANStar:
                  selfEdges: bool = True, merged: bool = False):
         """FirstStep's leaf branch on one large partition (FirstStep.java:104-108):
         calculateCoreDistances + the exact MRD MST (constructMSTBoruvka's weights and edge
-        order) in one call sharing one spatial index.  Returns (core, UndirectedGraph).
+        order) in one call -- sharing one spatial index for K2b's shapes, calculateCoreDistances
+        followed by K2g for every other distanceFunction and d.  Returns (core, UndirectedGraph).
         merged: the edges in the reducers' merge order (UnionFindReducer.java:19-69 +
         SortMST.java:9-17) -- what sort_edges_desc returns for the plain list -- without the
         re-sort (HDB_EDGES_MERGED)."""

@@ -206,27 +206,44 @@ int hdb_prim_mst_batched(hdb_ctx *ctx, const double *X, const int64_t *offsets, 
 int hdb_leaf_msts(hdb_ctx *ctx, const double *X, const int64_t *offsets, int32_t P, int32_t d, const int32_t *ids,
                   int32_t min_pts, int32_t metric, double *core_out, int32_t *va, int32_t *vb, double *w);
 
-/* Exact minimum spanning tree of the mutual-reachability graph for large n (Boruvka,
- * K2b).  Any MST: the sorted weight sequence equals the reference Prim's exactly; the
+/* Exact minimum spanning tree of the mutual-reachability graph for large n (Boruvka), for
+ * every HDB_METRIC_* and every d >= 1 that hdb_core_distances accepts; n < 2^31 (int32 ids).
+ * Any MST: the sorted weight sequence equals the reference Prim's exactly; the
  * topology can differ only among equal-weight edges (ties broken by (w, min id, max id)).
  * Outputs n-1 edges (va < vb, by the library's order), then n self edges if self_edges.
  *
- * Exactly: the unique MST under the strict total edge order (w, s, min id, max id), with
- * w = max(sqrt(s), core_p, core_q) (HDBSCANStar.java:162-168) and s the squared distance summed
- * in dimension order.  Non-finite and signed-zero input (the same for hdb_exact_mst):
+ * Exactly: the unique MST under the strict total edge order (w, s, min id, max id).
+ *   w  the reference's weight (HDBSCANStar.java:162-168): the pair's distance, replaced by
+ *      core_p, then by core_q, on a strict '>' only.
+ *   s  the tie key below w.  Euclidean: the squared distance summed in dimension order (w
+ *      starts from sqrt(s)).  Every other metric: the pair's distance itself, in the
+ *      reference's operation order (no contraction).
+ * Two paths, one contract.  Euclidean with d in {1,2,3,4,8,16} runs K2b (Morton/BVH index).
+ * Everything else runs K2g, a tiled all-pairs FP64 scan (kernel timers "boruvka_gen_scan" and
+ * "boruvka_gen_total", stats "boruvka_gen_rounds" = rounds of the last call and
+ * "boruvka_gen_qt" / "_ct" / "_dc" = its query tile, candidate tile and dimension chunk).
+ * For a Euclidean input both keys are the same, so the two paths agree edge for edge.
+ * Weights and tie keys can be negative on K2g: cosine and Pearson distances are 1 - x with x
+ * rounded, and x can exceed 1 by a few ulps (rows that are positive multiples of one another).
+ * Every non-NaN double is ordered numerically; a tree edge may then weigh less than zero and
+ * comes back as computed, and the edge list ascends numerically.  (The hierarchy calls'
+ * contracts on weights are unchanged.)
+ * Non-finite and signed-zero input (the same for hdb_exact_mst):
  *  - A pair whose mutual-reachability distance is NaN (a NaN coordinate; inf - inf in one
  *    coordinate) is not an edge.
  *  - A row with an infinite coordinate, a squared distance that overflows or an infinite core
  *    gives edges of weight +inf.  They are edges like any other and fall under the same tie
- *    rule: among +inf weights the smaller s wins, then the smaller ids.  (The device rounds
+ *    rule: among +inf weights the smaller s wins, then the smaller ids.  (K2b's device rounds
  *    find the finite edges; the +inf edges that join what is left are chosen on the host, stat
- *    "boruvka_inf_edges".)
+ *    "boruvka_inf_edges".  K2g keeps "no edge yet" apart from the weight and finds +inf edges
+ *    on the device like any other; it does not count them in that stat.)
  *  - Input whose non-NaN pairs do not connect all rows (e.g. any row with a NaN coordinate) is
  *    HDB_EINVAL with a message that names "non-finite input", the number of unreachable rows
  *    and the first of them.  No output is defined then; the context stays usable.
  *  - A NaN core never raises a weight (the reference's '>' comparisons), and neither does a
  *    -0.0 core: weights compare as numbers, so -0.0 acts as +0.0.  A tree edge's weight is
- *    never -0.0 (it starts from sqrt(s) >= +0.0 and only a strictly larger core replaces it);
+ *    never -0.0 (it starts from a distance that is not -0.0 -- sqrt(s) >= +0.0, a sum of
+ *    absolute values, 1 - x -- and only a strictly larger core replaces it);
  *    a self edge's weight is the core as passed, so a -0.0 core comes back as -0.0 there. */
 int hdb_mst_boruvka(hdb_ctx *ctx, const double *X, int64_t n, int32_t d, const double *core, int32_t metric,
                     int32_t self_edges, int32_t *va, int32_t *vb, double *w);
@@ -234,8 +251,10 @@ int hdb_mst_boruvka(hdb_ctx *ctx, const double *X, int64_t n, int32_t d, const d
 /* FirstStep's leaf branch for one large partition in one call (FirstStep.java:104-108:
  * HDBSCANStar.calculateCoreDistances then constructMST): core distances (semantics as
  * hdb_core_distances, bit-identical) and the exact mutual-reachability MST of
- * hdb_mst_boruvka (same weights and edge order), sharing one spatial index; the k-NN lists
- * seed every Boruvka round.  core_out nullable.  Local vertex ids 0..n-1.
+ * hdb_mst_boruvka (same weights and edge order), for every metric and d it accepts.  K2b's
+ * shapes share one spatial index and the k-NN lists seed every Boruvka round; every other
+ * shape is hdb_core_distances (so Euclidean 16 < d <= 256 with n >= 2048 takes its MFMA path)
+ * followed by K2g.  core_out nullable.  Local vertex ids 0..n-1.
  * NaN pairs, +inf weights and rows that no non-NaN pair reaches (HDB_EINVAL, "non-finite
  * input") are handled exactly as documented at hdb_mst_boruvka; core_out is then undefined. */
 #define HDB_EDGES_SELF 1   /* append the n self edges (HDBSCANStar.java:196-203)                  */
