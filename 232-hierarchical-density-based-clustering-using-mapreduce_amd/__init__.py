@@ -16,8 +16,8 @@ from .formats import (MapperDataset_github, double_to_string, format_cluster_tre
                       format_local_mst, format_outlier_scores, hierarchy_levels, parse_constraints, parse_local_mst, read_dataset)
 from .hdbscanstar import (CosineSimilarity, DistanceCalculator, EuclideanDistance, HDBSCANStar,
                           ManhattanDistance, PearsonCorrelation, SupremumDistance, UndirectedGraph,
-                          ClusterTree, ConstrainedLabels, cluster_tree, cluster_tree_bound,
-                          constrained_flat_labels, distance_rows, flat_labels,
-                          labels_at_levels, outlier_ranking, outlier_scores)
+                          ClusterTree, ConstrainedLabels, Prediction, approximate_predict, cluster_tree,
+                          cluster_tree_bound, constrained_flat_labels, distance_rows, flat_labels,
+                          labels_at_levels, outlier_ranking, outlier_scores, predict_labels)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

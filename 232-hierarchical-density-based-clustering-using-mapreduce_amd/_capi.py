@@ -99,6 +99,8 @@ def lib():
             "hdb_mst_boruvka": [vp, dp, i64, i32, dp, i32, i32, ip, ip, dp],
             "hdb_exact_mst": [vp, dp, i64, i32, i32, i32, i32, i32, dp, ip, ip, dp],
             "hdb_nearest_sample": [vp, dp, i64, dp, i64, i32, i32, ip, ip, ip, dp],
+            "hdb_attach_points": [vp, dp, i64, i32, dp, dp, i64, i32, i32, dp, ip, dp],
+            "hdb_attach_points_splits": [vp, dp, i64, i32, dp, dp, i64, i32, i32, i32, dp, ip, dp],
             "hdb_bubble_stats": [vp, dp, i64, i32, ip, i64, i32, dp, dp, dp, dp],
             "hdb_bubble_partials": [vp, dp, i64, i32, ip, i64, lp, i32, dp, dp, dp],
             "hdb_bubble_combine": [vp, dp, dp, dp, i32, i64, i32, dp, dp, dp, dp],
@@ -113,6 +115,7 @@ def lib():
             "hdb_flat_outlier_scores": [vp, ip, ip, dp, i64, i64, i32, dp, dp, ip, lp],
             "hdb_flat_cluster_tree": [vp, ip, ip, dp, i64, i64, i32, i64, lp, ip, dp, dp, dp, ip, ip, ip, ip, dp, lp],
             "hdb_labels_at_levels": [vp, ip, dp, i64, ip, dp, i64, dp, i32, ip],
+            "hdb_predict_labels": [vp, ip, dp, dp, ip, i64, ip, dp, i64, ip, dp, i64, ip, ip, dp],
             "hdb_constrained_flat_labels": [vp, ip, dp, ip, i64, ip, i64, ip, ip, ip, i64, ip, ip, dp, ip, ip, lp],
             "hdb_local_mst_ids": [vp, ip, i64, ip, ip, dp, i64, i32, ip, ip, ip],
             "hdb_comm_unique_id": [vp, i32],
@@ -148,7 +151,8 @@ EXPORTED = ["hdb_ctx_create", "hdb_ctx_destroy", "hdb_ctx_set_stream", "hdb_ctx_
             "hdb_leaf_msts", "hdb_mst_boruvka", "hdb_exact_mst", "hdb_nearest_sample", "hdb_bubble_stats",
             "hdb_bubble_partials", "hdb_bubble_combine", "hdb_bubble_core_distances", "hdb_bubble_prim_mst", "hdb_local_model", "hdb_local_model_cores", "hdb_quicksort_edges",
             "hdb_merge_sorted_runs", "hdb_sort_edges_desc", "hdb_flat_labels", "hdb_flat_outlier_scores", "hdb_flat_cluster_tree",
-            "hdb_cluster_tree_bound", "hdb_labels_at_levels", "hdb_constrained_flat_labels", "hdb_format_double", "hdb_parse_points",
+            "hdb_cluster_tree_bound", "hdb_labels_at_levels", "hdb_constrained_flat_labels",
+            "hdb_attach_points", "hdb_attach_points_splits", "hdb_predict_labels", "hdb_format_double", "hdb_parse_points",
             "hdb_format_mst_records", "hdb_parse_mst_records", "hdb_comm_unique_id", "hdb_comm_init",
             "hdb_comm_destroy", "hdb_free", "hdb_copy", "hdb_merge_edges", "hdb_local_mst_ids"]
 

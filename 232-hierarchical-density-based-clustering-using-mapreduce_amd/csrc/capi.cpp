@@ -276,6 +276,30 @@ int hdb_nearest_sample(hdb_ctx *ctx, const double *X, int64_t n, const double *S
     });
 }
 
+int hdb_attach_points(hdb_ctx *ctx, const double *X, int64_t n, int32_t d, const double *core, const double *Q,
+                      int64_t m, int32_t min_pts, int32_t metric, double *core_q, int32_t *nearest, double *level) {
+    return hdb_attach_points_splits(ctx, X, n, d, core, Q, m, min_pts, metric, 0, core_q, nearest, level);
+}
+
+int hdb_attach_points_splits(hdb_ctx *ctx, const double *X, int64_t n, int32_t d, const double *core,
+                             const double *Q, int64_t m, int32_t min_pts, int32_t metric, int32_t attach_splits,
+                             double *core_q, int32_t *nearest, double *level) {
+    return guarded(ctx, [&] {
+        check_metric(metric);
+        if (attach_splits < 0 || attach_splits > 65535) HDB_THROW(HDB_EINVAL, "attach_splits must be in 0..65535");
+        if (n < 0 || m < 0 || d <= 0 || min_pts < 1 || (n > 0 && (!X || !core)) || (m > 0 && (!Q || !nearest || !level)))
+            HDB_THROW(HDB_EINVAL, "bad arguments");
+        if (n > (int64_t)INT32_MAX) HDB_THROW(HDB_EINVAL, "attach: n must be below 2^31 (int32 ids)");
+        Stager s(ctx);
+        const double *dX = s.in(X, (size_t)n * d), *dc = s.in(core, (size_t)n);
+        const double *dQ = s.in(Q, (size_t)m * d);
+        double *dcq = s.out(core_q, (size_t)m), *dl = s.out(level, (size_t)m);
+        int32_t *dn = s.out(nearest, (size_t)m);
+        attach_points_device(ctx, dX, n, d, dc, dQ, m, min_pts, metric, attach_splits, dcq, dn, dl);
+        s.finish();
+    });
+}
+
 int hdb_bubble_stats(hdb_ctx *ctx, const double *X, int64_t n, int32_t d, const int32_t *bubble_of, int64_t nb,
                      int32_t variant, double *ls, double *ss, double *rep, double *info) {
     return guarded(ctx, [&] {
@@ -635,6 +659,41 @@ int hdb_labels_at_levels(hdb_ctx *ctx, const int32_t *parent, const double *birt
         const double *dlv = sg.in(levels, (size_t)L);
         int32_t *dout = sg.out(labels_out, (size_t)L * (size_t)n);
         labels_at_levels_device(ctx, dp, db, K, dpc, dpl, n, dlv, L, dout);
+        sg.finish();
+    });
+}
+
+int hdb_predict_labels(hdb_ctx *ctx, const int32_t *parent, const double *birth, const double *death,
+                       const int32_t *flat_label, int64_t K, const int32_t *point_cluster,
+                       const double *point_level, int64_t n, const int32_t *nearest, const double *level,
+                       int64_t m, int32_t *tree_label, int32_t *labels, double *scores) {
+    const bool bad = K < 0 || n < 0 || m < 0 || (K > 0 && (!parent || !birth || !death || !flat_label)) ||
+                     (n > 0 && (!point_cluster || !point_level)) || (m > 0 && (!nearest || !level));
+    if (!ctx) {  // host-only use (all pointers in host memory): no device needed
+        try {
+            if (bad) HDB_THROW(HDB_EINVAL, "bad arguments");
+            return predict_labels_host(parent, birth, death, flat_label, K, point_cluster, point_level, n, nearest,
+                                       level, m, tree_label, labels, scores);
+        } catch (const Error &e) {
+            set_error(e.msg);
+            return e.code;
+        } catch (const std::bad_alloc &) {
+            set_error("host allocation failed");
+            return HDB_ENOMEM;
+        }
+    }
+    return guarded(ctx, [&] {
+        if (bad) HDB_THROW(HDB_EINVAL, "bad arguments");
+        if (m == 0) return;
+        Stager sg(ctx);
+        const size_t nk = (size_t)K, np = (size_t)n, nm = (size_t)m;
+        const int32_t *dp = sg.in(parent, nk), *dfl = sg.in(flat_label, nk), *dpc = sg.in(point_cluster, np);
+        const double *db = sg.in(birth, nk), *dd = sg.in(death, nk), *dpl = sg.in(point_level, np);
+        const int32_t *dnr = sg.in(nearest, nm);
+        const double *dlv = sg.in(level, nm);
+        int32_t *dtl = sg.out(tree_label, nm), *dlab = sg.out(labels, nm);
+        double *dsc = sg.out(scores, nm);
+        predict_labels_device(ctx, dp, db, dd, dfl, K, dpc, dpl, n, dnr, dlv, m, dtl, dlab, dsc);
         sg.finish();
     });
 }

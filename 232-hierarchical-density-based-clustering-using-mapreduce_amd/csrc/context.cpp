@@ -269,6 +269,7 @@ int hdb_ctx_create(int device, hdb_ctx **out) {
                               "boruvka_visits_sum", "boruvka_evals_sum", "boruvka_bound_ns_sum", "boruvka_inf_edges"})
             c->stats[k] = 0;
         boruvka_generic_stats_init(c);
+        attach_stats_init(c);
         // per-kernel HIP-event timing from birth (contexts created on worker threads, bench.py)
         if (const char *e = getenv("HDB_KERNEL_TIMING")) c->timing = atoi(e) != 0;
         // A/B runs of unmodified programs: HDB_OPTS="name=value,name=value", every pair applied

@@ -347,4 +347,60 @@ int labels_at_levels_host(const int32_t *parent, const double *birth, int64_t K,
     return HDB_OK;
 }
 
+// hdb_predict_labels on host arrays: the plain walk.  Query i attached at (y, e) = (nearest[i],
+// level[i]) starts at point_cluster[y] and climbs while birth <= e (the root's NaN birth stops it);
+// its flat label is that of the nearest selected cluster from there to the root; its score is GLOSH
+// at eps = max(e, point_level[y]) with the eps_max of hdb_flat_outlier_scores (the subtree minimum
+// of death; the root takes its descendants only, from Double.MAX_VALUE).  Minima are taken under
+// the order of the device's integer keys (-0.0 below +0.0), so both paths give the same bits.
+int predict_labels_host(const int32_t *parent, const double *birth, const double *death, const int32_t *flat_label,
+                        int64_t K, const int32_t *point_cluster, const double *point_level, int64_t n,
+                        const int32_t *nearest, const double *level, int64_t m, int32_t *tree_label, int32_t *labels,
+                        double *scores) {
+    if (K < 0 || n < 0 || m < 0) HDB_THROW(HDB_EINVAL, "bad arguments");
+    if (m == 0) return HDB_OK;
+    if (K >= (int64_t(1) << 30)) HDB_THROW(HDB_EINVAL, "predict labels: too many clusters");
+    if (K > 0 && parent[0] != 0) HDB_THROW(HDB_EINVAL, "predict labels: the root (label 1) must have parent 0");
+    for (int64_t i = 1; i < K; i++)
+        if (parent[i] < 0 || parent[i] > i) HDB_THROW(HDB_EINVAL, "predict labels: parent label out of range");
+    for (int64_t v = 0; v < n; v++)
+        if (point_cluster[v] < 1 || point_cluster[v] > K)
+            HDB_THROW(HDB_EINVAL, "predict labels: point_cluster out of range");
+    for (int64_t i = 0; i < m; i++)
+        if (nearest[i] < -1 || nearest[i] >= n) HDB_THROW(HDB_EINVAL, "predict labels: nearest out of range");
+    for (int64_t i = 0; i < m; i++)
+        if (nearest[i] >= 0 && level[i] != level[i]) HDB_THROW(HDB_EINVAL, "predict labels: NaN level");
+    auto key = [](double x) {
+        uint64_t u;
+        std::memcpy(&u, &x, 8);
+        return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+    };
+    // by tree label (index 0: none): eps_max and the flat label of the nearest selected cluster
+    // on the way up; a parent's label is below its children's
+    std::vector<double> eps_max((size_t)K + 1, std::numeric_limits<double>::max());
+    std::vector<int32_t> near((size_t)K + 1, 0);
+    for (int64_t c = 2; c <= K; c++) eps_max[c] = death[c - 1];
+    for (int64_t c = K; c >= 2; c--) {
+        const int32_t p = parent[c - 1];
+        if (p > 0 && key(eps_max[c]) < key(eps_max[p])) eps_max[p] = eps_max[c];
+    }
+    for (int64_t c = 1; c <= K; c++) near[c] = flat_label[c - 1] != 0 ? flat_label[c - 1] : near[parent[c - 1]];
+    for (int64_t i = 0; i < m; i++) {
+        const int32_t y = nearest[i];
+        int32_t C = 0;
+        double sc = 1.0;
+        if (y >= 0) {
+            const double e = level[i];
+            C = point_cluster[y];
+            while (C > 0 && birth[C - 1] <= e) C = parent[C - 1];
+            const double pl = point_level[y], eps = pl > e ? pl : e;
+            sc = eps == 0.0 ? 0.0 : 1.0 - eps_max[C] / eps;  // C == 0 (a malformed tree's walk): MAX_VALUE
+        }
+        if (tree_label) tree_label[i] = C;
+        if (labels) labels[i] = near[C];
+        if (scores) scores[i] = sc;
+    }
+    return HDB_OK;
+}
+
 }  // namespace hdb

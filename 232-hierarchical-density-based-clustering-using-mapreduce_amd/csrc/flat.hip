@@ -1947,6 +1947,98 @@ __global__ __launch_bounds__(CUT_TB) void lc_cut(const int32_t *__restrict__ anc
     flag_or(err, e);
 }
 
+// ------------------------------------------------------------------ 9. out-of-sample labels
+// hdb_predict_labels: a query attached to training point y at level e starts at C = last(y) and
+// climbs while birth[C] <= e -- the level cut's climb without its noise rule, over the same
+// ancestor tables (lc_init / lc_double).  Two more tables by tree label, built with the same rows:
+// eps_max (the subtree minimum of death as an ord_enc key; the root starts from Double.MAX_VALUE
+// and takes its descendants only) by atomic minima into the 2^j-th ancestor, and the flat label
+// of the nearest selected cluster on the way to the root by pointer doubling.  Index 0 ("none")
+// keeps Double.MAX_VALUE and label 0.  The input is validated, never trusted: every index is bounded.
+enum : int { PE_NEAREST = 8, PE_LEVEL = 16 };
+
+__global__ void pr_init(const double *__restrict__ death, const int32_t *__restrict__ flat_label, int32_t K,
+                        unsigned long long *__restrict__ em, int32_t *__restrict__ near) {
+    HDB_GRID_STRIDE(i, (int64_t)K + 1) {
+        em[i] = ord_enc(i >= 2 ? death[i - 1] : DBL_MAX);
+        near[i] = i >= 1 ? flat_label[i - 1] : 0;
+    }
+}
+// after round j: em[a] covers a's descendants less than 2^(j+1) levels down (a value read while
+// others lower it only covers more of the reader's own subtree); near covers 2^(j+1) path nodes
+__global__ void pr_double(const int32_t *__restrict__ ancj, int32_t K, unsigned long long *__restrict__ em,
+                          const int32_t *__restrict__ near_in, int32_t *__restrict__ near_out) {
+    HDB_GRID_STRIDE(i, (int64_t)K + 1) {
+        const int32_t a = ancj[i];  // 0..K by construction
+        if (a > 0) {
+            const unsigned long long v = u64_ld(em + i);
+            if (v < u64_ld(em + a)) atomicMin(em + a, v);
+        }
+        const int32_t x = near_in[i];
+        near_out[i] = x != 0 ? x : near_in[a];
+    }
+}
+__global__ void pr_check_points(const int32_t *__restrict__ point_cluster, int64_t n, int32_t K, int *__restrict__ err) {
+    int e = 0;
+    HDB_GRID_STRIDE(v, n) {
+        const int32_t c = point_cluster[v];
+        if (c < 1 || c > K) e = LE_POINT;
+    }
+    flag_or(err, e);
+}
+__global__ __launch_bounds__(256) void pr_walk(const int32_t *__restrict__ anc, const double *__restrict__ bt, int32_t K,
+                                                int J, const unsigned long long *__restrict__ em,
+                                                const int32_t *__restrict__ near,
+                                                const int32_t *__restrict__ point_cluster,
+                                                const double *__restrict__ point_level, int64_t n,
+                                                const int32_t *__restrict__ nearest, const double *__restrict__ level,
+                                                int64_t m, int32_t *__restrict__ tree_label,
+                                                int32_t *__restrict__ labels, double *__restrict__ scores,
+                                                int *__restrict__ err) {
+    const int64_t stride = (int64_t)K + 1;
+    int e = 0;
+    for (int64_t base = (int64_t)blockIdx.x * 256; base < m; base += (int64_t)gridDim.x * 256) {  // uniform trips
+        const int64_t i = base + threadIdx.x;
+        if (i >= m) continue;
+        const int32_t y = nearest[i];
+        int32_t cur = 0;
+        double sc = 1.0;
+        if (y < -1 || y >= n) {
+            e |= PE_NEAREST;
+        } else if (y >= 0) {
+            const double eps = level[i];
+            int32_t c0 = point_cluster[y];
+            if (c0 < 1 || c0 > K) c0 = 0;  // reported by pr_check_points
+            if (eps != eps) {
+                e |= PE_LEVEL;
+            } else {
+                cur = c0;
+                if (bt[cur] <= eps) {  // lc_cut's climb: gallop up the rows, descend over the lower ones
+                    int j = 0;
+                    int32_t last = cur;
+                    while (j < J) {
+                        const int32_t a = anc[j * stride + cur];
+                        if (!(bt[a] <= eps)) break;  // a == 0 has a NaN birth
+                        last = a;
+                        j++;
+                    }
+                    for (int jj = j - 2; jj >= 0; jj--) {
+                        const int32_t a = anc[jj * stride + last];
+                        if (bt[a] <= eps) last = a;
+                    }
+                    cur = anc[last];
+                }
+                const double pl = point_level[y], ee = pl > eps ? pl : eps;
+                sc = ee == 0.0 ? 0.0 : 1.0 - ord_dec(em[cur]) / ee;
+            }
+        }
+        if (tree_label) tree_label[i] = cur;
+        if (labels) labels[i] = near[cur];
+        if (scores) scores[i] = sc;
+    }
+    flag_or(err, e);
+}
+
 // zero-initialised FOSC block: nch, kcur, plen, maxld (+ counters), pwide, a spare (m ints
 // each: 24m bytes, so the u64 array after them is 8-byte aligned), hkey (m u64), 192 jump flags
 inline size_t fz_layout(int64_t m) { return (size_t)m * 24 + (size_t)m * 8 + 192 * 4; }
@@ -2464,6 +2556,57 @@ void labels_at_levels_device(hdb_ctx *ctx, const int32_t *parent, const double *
     if (L == 0 || n == 0) return;  // as the host: the tree is not looked at
     if (e & LE_PARENT) HDB_THROW(HDB_EINVAL, "labels at levels: parent label out of range");
     if (e & LE_POINT) HDB_THROW(HDB_EINVAL, "labels at levels: point cluster out of range");
+}
+
+void predict_labels_device(hdb_ctx *ctx, const int32_t *parent, const double *birth, const double *death,
+                           const int32_t *flat_label, int64_t K, const int32_t *point_cluster,
+                           const double *point_level, int64_t n, const int32_t *nearest, const double *level,
+                           int64_t m, int32_t *tree_label, int32_t *labels, double *scores) {
+    if (K < 0 || n < 0 || m < 0) HDB_THROW(HDB_EINVAL, "bad arguments");
+    if (m == 0) return;
+    if (K >= (int64_t(1) << 30)) HDB_THROW(HDB_EINVAL, "predict labels: too many clusters");
+    hipStream_t st = ctx->stream;
+    KernelTimer tt(ctx, "predict_labels");
+    int J = 1;
+    while ((int64_t(1) << J) < K) J++;  // 2^J >= K > the deepest chain
+    const int64_t stride = K + 1;
+    Carver probe;
+    auto layout = [&](Carver &cv) {
+        cv.take<int64_t>(1);                     // error word
+        cv.take<double>(stride);                 // births by label
+        cv.take<int32_t>(stride * J);            // ancestor rows
+        cv.take<unsigned long long>(stride);     // eps_max keys
+        for (int k = 0; k < 2; k++) cv.take<int32_t>(stride);  // nearest selected flat label, two buffers
+    };
+    layout(probe);
+    Carver cv{(char *)arena(ctx, A_FLAT1, probe.off), 0};
+    int *err = (int *)cv.take<int64_t>(1);
+    double *bt = cv.take<double>(stride);
+    int32_t *anc = cv.take<int32_t>(stride * J);
+    unsigned long long *em = cv.take<unsigned long long>(stride);
+    int32_t *near_a = cv.take<int32_t>(stride), *near_b = cv.take<int32_t>(stride);
+    HIP_CHECK(hipMemsetAsync(err, 0, sizeof(int64_t), st));
+    const int gk = grid_for(stride);
+    hipLaunchKernelGGL(lc_init, dim3(gk), dim3(256), 0, st, parent, birth, (int32_t)K, anc, bt, err);
+    for (int j = 1; j < J; j++)
+        hipLaunchKernelGGL(lc_double, dim3(gk), dim3(256), 0, st, anc + (j - 1) * stride, anc + j * stride, (int32_t)K);
+    hipLaunchKernelGGL(pr_init, dim3(gk), dim3(256), 0, st, death, flat_label, (int32_t)K, em, near_a);
+    for (int j = 0; j < J; j++) {
+        hipLaunchKernelGGL(pr_double, dim3(gk), dim3(256), 0, st, anc + j * stride, (int32_t)K, em, near_a, near_b);
+        std::swap(near_a, near_b);
+    }
+    if (n > 0) hipLaunchKernelGGL(pr_check_points, dim3(grid_for(n)), dim3(256), 0, st, point_cluster, n, (int32_t)K, err);
+    hipLaunchKernelGGL(pr_walk, dim3(grid_for(m)), dim3(256), 0, st, anc, bt, (int32_t)K, J, em, near_a, point_cluster,
+                       point_level, n, nearest, level, m, tree_label, labels, scores, err);
+    HIP_CHECK(hipGetLastError());
+    int64_t *pin = pinned_words(ctx) + PINNED_WORDS - 8;
+    HIP_CHECK(hipMemcpyAsync(pin, err, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    const int e = (int)pin[0];
+    if (e & LE_PARENT) HDB_THROW(HDB_EINVAL, "predict labels: parent label out of range");
+    if (e & LE_POINT) HDB_THROW(HDB_EINVAL, "predict labels: point_cluster out of range");
+    if (e & PE_NEAREST) HDB_THROW(HDB_EINVAL, "predict labels: nearest out of range");
+    if (e & PE_LEVEL) HDB_THROW(HDB_EINVAL, "predict labels: NaN level");
 }
 
 }  // namespace hdb

@@ -72,6 +72,14 @@ void boruvka_generic_device(hdb_ctx *ctx, const double *X, int64_t n, int d, con
                             int32_t *va, int32_t *vb, double *w);
 // its tile constants and round count as stats (boruvka_gen_qt / _ct / _dc / _rounds)
 void boruvka_generic_stats_init(hdb_ctx *ctx);
+// the attach scan of out-of-sample prediction (attach.hip): per query row its core distance
+// against the training rows (core_q, nullable) and its cheapest mutual-reachability edge into them
+// (nearest, level); splits: candidate columns over grid.y (0: chosen from m and n); all arrays on
+// the device, stream-ordered
+void attach_points_device(hdb_ctx *ctx, const double *X, int64_t n, int d, const double *core, const double *Q,
+                          int64_t m, int min_pts, int metric, int splits, double *core_q, int32_t *nearest,
+                          double *level);
+void attach_stats_init(hdb_ctx *ctx);  // stat attach_last_splits
 // K2b's infinite-weight tail on host arrays (inf_edges.cpp): X, core in id order; (ea, eb)[m] the
 // finite edges K2b found.  Writes the +inf edges that join their trees under (w, s, lo, hi) and
 // returns their count; rows_left / first_left: rows outside the largest tree that only NaN
@@ -108,6 +116,12 @@ void flat_cluster_tree_device(hdb_ctx *ctx, const int32_t *va, const int32_t *vb
 void labels_at_levels_device(hdb_ctx *ctx, const int32_t *parent, const double *birth, int64_t K,
                              const int32_t *point_cluster, const double *point_level, int64_t n,
                              const double *levels, int32_t L, int32_t *labels_out);
+// hdb_predict_labels: queries attached at (nearest, level) read their tree label, flat label and
+// GLOSH score out of a cluster tree; every output nullable; all arrays on the device; synchronises
+void predict_labels_device(hdb_ctx *ctx, const int32_t *parent, const double *birth, const double *death,
+                           const int32_t *flat_label, int64_t K, const int32_t *point_cluster,
+                           const double *point_level, int64_t n, const int32_t *nearest, const double *level,
+                           int64_t m, int32_t *tree_label, int32_t *labels, double *scores);
 // outputs of hdb_constrained_flat_labels: K entries per cluster array (entry i = tree label
 // i + 1), n labels, each nullable; n_clusters is a host scalar
 struct ConstrainedOut {
@@ -146,6 +160,10 @@ int flat_cluster_tree_host(const int32_t *va, const int32_t *vb, const double *w
 int labels_at_levels_host(const int32_t *parent, const double *birth, int64_t K, const int32_t *point_cluster,
                           const double *point_level, int64_t n, const double *levels, int32_t L,
                           int32_t *labels_out);
+int predict_labels_host(const int32_t *parent, const double *birth, const double *death, const int32_t *flat_label,
+                        int64_t K, const int32_t *point_cluster, const double *point_level, int64_t n,
+                        const int32_t *nearest, const double *level, int64_t m, int32_t *tree_label, int32_t *labels,
+                        double *scores);
 int quicksort_edges(int32_t *va, int32_t *vb, double *w, int64_t ne);
 // message of the last HDB_EREF_NEGATIVE_CLUSTER on this thread (cluster label, level, numPoints)
 const char *local_model_error_detail();

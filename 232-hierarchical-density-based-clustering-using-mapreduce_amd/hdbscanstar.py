@@ -234,6 +234,32 @@ class HDBSCANStar:
                                 A.ptr(idx)), "knn")
         return (dist, idx) if withIndices else dist
 
+    def attachPoints(self, dataSet, coreDistances, queries, k: int, distanceFunction=None, attach_splits: int = 0):
+        """The attach scan of out-of-sample prediction (hdb_attach_points): for every row of
+        ``queries`` its core distance against ``dataSet`` (the k - 1 nearest training rows, the
+        CORE_EXCL_SELF value of the query as one more row), the training row it reaches through
+        its cheapest mutual-reachability edge under the strict order (w, s, j) and that weight.
+        ``coreDistances`` are the training rows' core distances as the fit computed them.
+        Returns (core_q, nearest, level); a query without a candidate has nearest -1 and level
+        Double.MAX_VALUE.  Each array may be host or device memory; results live where
+        ``queries`` does.  ``attach_splits`` > 0 forces the number of candidate columns the scan
+        merges (hdb_attach_points_splits; no bit of the result depends on it)."""
+        X, core, Q = A.Arr(dataSet, np.float64), A.Arr(coreDistances, np.float64), A.Arr(queries, np.float64)
+        n, d = X.obj.shape
+        m = Q.obj.shape[0]
+        if Q.obj.ndim != 2 or Q.obj.shape[1] != d:
+            raise ValueError("queries must be m x d with the training rows' d")
+        if core.obj.shape[0] != n:
+            raise ValueError("coreDistances must have one entry per training row")
+        core_q, level = A.new_like(Q, (m,), np.float64), A.new_like(Q, (m,), np.float64)
+        nearest = A.new_like(Q, (m,), np.int32)
+        ref = next((x for x in (Q, X, core) if x.device is not None and x.device.type == "cuda"), Q)
+        c = _ctx(ref, self.ctx)
+        A.check(A.lib().hdb_attach_points_splits(c.h, X.p, n, d, core.p, Q.p, m, k, metric_of(distanceFunction),
+                                                 int(attach_splits), A.ptr(core_q), A.ptr(nearest), A.ptr(level)),
+                "attachPoints")
+        return core_q, nearest, level
+
 
 def flat_labels(va, vb, w, n: int, minClSize: int, ctx=None):
     """Global HDBSCAN* flat partition over a merged MST (the reference's
@@ -413,6 +439,56 @@ def labels_at_levels(tree: ClusterTree, levels, ctx=None):
                 break
     A.check(A.lib().hdb_labels_at_levels(h, par.p, bi.p, K, pc.p, pl.p, n, lv.p, L, A.ptr(out)), "labels_at_levels")
     return out
+
+
+def predict_labels(tree: ClusterTree, nearest, level, flat_label=None, ctx=None):
+    """hdb_predict_labels: queries attached to training point nearest[i] at level[i] read their
+    tree label (the walk of labels_at_levels from the point's last cluster, without its noise
+    rule), their flat label (``flat_label`` per cluster: the tree's own by default, or the one
+    constrained_flat_labels returns) and their GLOSH score at max(level, point_level[nearest]).
+    nearest -1: (0, 0, 1.0).  Returns (tree_labels, labels, scores) where ``nearest`` lives; host
+    arrays without a ctx run on the host with no device."""
+    par, bi, de = A.Arr(tree.parent, np.int32), A.Arr(tree.birth, np.float64), A.Arr(tree.death, np.float64)
+    fl = A.Arr(tree.flat_label if flat_label is None else flat_label, np.int32)
+    pc, pl = A.Arr(tree.point_cluster, np.int32), A.Arr(tree.point_level, np.float64)
+    nr, lv = A.Arr(nearest, np.int32), A.Arr(level, np.float64)
+    K, n, m = int(par.obj.shape[0]), int(pc.obj.shape[0]), int(nr.obj.shape[0])
+    if fl.obj.shape[0] != K or lv.obj.shape[0] != m:
+        raise ValueError("flat_label needs one entry per cluster, level one per query")
+    tl, lab = A.new_like(nr, (m,), np.int32), A.new_like(nr, (m,), np.int32)
+    sc = A.new_like(nr, (m,), np.float64)
+    h = ctx.h if ctx is not None else None
+    if h is None:
+        for x in (nr, lv, pc, par, fl):
+            if x.device is not None and x.device.type == "cuda":
+                h = A.Context.get(x.device.index or 0).h
+                break
+    A.check(A.lib().hdb_predict_labels(h, par.p, bi.p, de.p, fl.p, K, pc.p, pl.p, n, nr.p, lv.p, m, A.ptr(tl),
+                                       A.ptr(lab), A.ptr(sc)), "predict_labels")
+    return tl, lab, sc
+
+
+class Prediction:
+    """The result of approximate_predict, one entry per query: ``labels`` (flat; 0 = noise),
+    ``tree_labels``, ``nearest`` (the training row attached to, -1 = none), ``level`` (the
+    mutual-reachability weight of that edge), ``core`` (the query's core distance) and ``scores``
+    (GLOSH)."""
+
+    def __init__(self, labels, tree_labels, nearest, level, core, scores):
+        self.labels, self.tree_labels, self.nearest = labels, tree_labels, nearest
+        self.level, self.core, self.scores = level, core, scores
+
+
+def approximate_predict(tree: ClusterTree, X, core, Q, minPts: int, distanceFunction=None, flat_label=None,
+                        ctx=None) -> Prediction:
+    """fit, then predict: classifies rows that were not in the fit without refitting.  Each row
+    of Q is attached to the fitted hierarchy through its cheapest mutual-reachability edge into
+    the training rows X (HDBSCANStar.attachPoints; ``core`` = their core distances, e.g. from
+    exactMST) and reads the cluster at that level out of ``tree`` (predict_labels).  Tensors in
+    give tensors out; the results live where Q does."""
+    core_q, nearest, level = HDBSCANStar(ctx).attachPoints(X, core, Q, minPts, distanceFunction)
+    tl, lab, sc = predict_labels(tree, nearest, level, flat_label, ctx=ctx)
+    return Prediction(lab, tl, nearest, level, core_q, sc)
 
 
 MUST_LINK, CANNOT_LINK = 0, 1  # HDB_CONSTRAINT_*

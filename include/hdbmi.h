@@ -289,6 +289,42 @@ int hdb_nearest_sample(hdb_ctx *ctx, const double *X, int64_t n, const double *S
                        int32_t metric, const int32_t *x_key, const int32_t *s_key, int32_t *nearest_out,
                        double *dist_out);
 
+/* --------------------------------------------------------- out-of-sample prediction: the attach scan
+ * Attaches m query rows Q (m x d) to a fitted set: X (n x d) training rows and core (n), their
+ * core distances as passed -- whatever semantics the fit used.  Everything is exact, in the
+ * reference's operation order (no contraction); all five metrics, every d >= 1.
+ *   dist(i, j)  DistanceCalculator.computeDistance(Q[i], X[j]), the query row first: the bits of
+ *               hdb_distance_rows.
+ *   core_q[i]   (m, nullable) entry K - 1 of the ascending list of the K = min_pts - 1 smallest
+ *               dist(i, j) over all n training rows, filled by the reference's strict '<' insertion
+ *               into a Double.MAX_VALUE buffer (HDBSCANStar.java:79-97): a NaN distance, or one not
+ *               below Double.MAX_VALUE, never enters, and fewer than K candidates leave
+ *               Double.MAX_VALUE -- the core distance HDB_CORE_EXCL_SELF gives the query as the last
+ *               row of [X; Q[i]].  min_pts == 1: 0.  min_pts outside 1..32: HDB_EINVAL, as
+ *               hdb_core_distances.
+ *   w(i, j)     dist(i, j), replaced by core_q[i], then by core[j], on a strict '>' only
+ *               (HDBSCANStar.java:162-168): a NaN core never raises a weight, a -0.0 core acts as
+ *               +0.0.  A pair whose w is NaN is no candidate; +inf is a candidate like any other.
+ *   nearest[i]  (m) the j that minimises the strict total order (w, s, j), s as in hdb_mst_boruvka:
+ *               Euclidean: the squared distance summed in dimension order; every other metric: the
+ *               distance itself.  Negative cosine and Pearson values are ordered numerically.
+ *   level[i]    (m) that w.
+ * A query without a candidate (a NaN query row, only NaN weights, n == 0): nearest = -1, level =
+ * Double.MAX_VALUE.  m == 0: HDB_OK.  n >= 2^31: HDB_EINVAL.  Pointer rules as hdb_knn: host or
+ * device per pointer, stream-ordered when all pointers are device memory.
+ * Two passes of one tiled all-pairs FP64 scan (kernel timers "attach_knn": the lists, "attach_min":
+ * the arg-min), the training rows split over workgroup columns whose partial lists and partial
+ * (w, s, j) minima a second kernel merges; the column count changes no bit of the output.
+ * hdb_attach_points_splits is the same call with that count as an argument: attach_splits = 0
+ * chooses it from m and n (what hdb_attach_points does), 1..65535 forces it (columns past the last
+ * tile are empty), anything else is HDB_EINVAL; stat "attach_last_splits" = the count of the last
+ * call.  The count is an argument of the call, not a context option: nothing is left set. */
+int hdb_attach_points(hdb_ctx *ctx, const double *X, int64_t n, int32_t d, const double *core, const double *Q,
+                      int64_t m, int32_t min_pts, int32_t metric, double *core_q, int32_t *nearest, double *level);
+int hdb_attach_points_splits(hdb_ctx *ctx, const double *X, int64_t n, int32_t d, const double *core,
+                             const double *Q, int64_t m, int32_t min_pts, int32_t metric, int32_t attach_splits,
+                             double *core_q, int32_t *nearest, double *level);
+
 /* --------------------------------------------------------- bubble statistics (a11, a12)
  * Bulk CombineStep (CombineStep.java:18-64) over a partition: member order = ascending
  * point index (D5).  Outputs per bubble: ls, ss, rep (nb*d), info (nb*3: extent, nnDist, n).
@@ -515,6 +551,29 @@ int64_t hdb_cluster_tree_bound(int64_t n, int32_t min_cl_size);
 int hdb_labels_at_levels(hdb_ctx *ctx, const int32_t *parent, const double *birth, int64_t K,
                          const int32_t *point_cluster, const double *point_level, int64_t n,
                          const double *levels, int32_t L, int32_t *labels_out);
+
+/* Out-of-sample labels from the arrays of hdb_flat_cluster_tree (flat_label may equally be the one
+ * hdb_constrained_flat_labels returns) and the (nearest, level) pairs of hdb_attach_points.  For
+ * query i, y = nearest[i] and e = level[i]:
+ *   tree_label[i]  start at C = point_cluster[y] and move to parent[C] while birth[C] <= e (the
+ *                  root's NaN birth stops the walk).  No noise rule: a query that reaches y below
+ *                  y's own level shares y's last cluster, as y's own flat label does.
+ *   labels[i]      the flat_label of the nearest selected cluster on the path from C to the root,
+ *                  C included; 0 if there is none.
+ *   scores[i]      eps = max(e, point_level[y]); eps == 0 ? 0.0 : 1.0 - eps_max(C) / eps, eps_max as
+ *                  in hdb_flat_outlier_scores: the subtree minimum of death, for the root its
+ *                  descendants only (Double.MAX_VALUE for a root that never splits).
+ * nearest[i] == -1: tree label 0, label 0, score 1.0.  Every output is nullable.  m == 0: HDB_OK.
+ * The input is validated, never trusted (no out-of-bounds access on host or device): nearest
+ * outside -1..n-1, a NaN level where nearest >= 0, and the tree checks of hdb_labels_at_levels
+ * give HDB_EINVAL with a message naming the field.  Pointer rules as hdb_labels_at_levels: host,
+ * device or mixed, ctx may be NULL when every pointer is host memory; both paths give the same
+ * bits.  The device climbs by the level cut's binary lifting (kernel timer "predict_labels").
+ * Synchronises. */
+int hdb_predict_labels(hdb_ctx *ctx, const int32_t *parent, const double *birth, const double *death,
+                       const int32_t *flat_label, int64_t K, const int32_t *point_cluster,
+                       const double *point_level, int64_t n, const int32_t *nearest, const double *level,
+                       int64_t m, int32_t *tree_label, int32_t *labels, double *scores);
 
 /* Semi-supervised flat extraction (Main.java:49,434-436 "constraints=<file>"; Constraint.java,
  * HDBSCANStar.calculateNumConstraintsSatisfied :738-789, the constraint branches of
