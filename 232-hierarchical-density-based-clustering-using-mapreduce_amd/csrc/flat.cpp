@@ -96,7 +96,9 @@ int flat_host_impl(const int32_t *va, const int32_t *vb, const double *w, int64_
     std::vector<std::vector<int32_t>> groups;
     for (size_t g0 = 0; g0 < e.size();) {
         size_t g1 = g0;
-        const double lev = w[e[g0]];
+        // -0.0 and 0.0 are one level, +0.0 whichever edge leads the group: 1 / level (the
+        // stability terms here and at the children born at it) and the GLOSH level read this value
+        const double lev = w[e[g0]] == 0.0 ? 0.0 : w[e[g0]];
         while (g1 < e.size() && w[e[g1]] == lev) g1++;
         const size_t m = g1 - g0;
         pre_a.resize(m);

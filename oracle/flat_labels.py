@@ -7,6 +7,7 @@ It follows the canonical top-down procedure of HDBSCANStar.computeHierarchyAndCl
 findProminentClusters (:567-625), without constraints, with these canonical choices where the
 Java's result depends on container iteration order (documented in DESIGN.md, "flat labels"):
 
+  * -0.0 and 0.0 are one level, +0.0 (1 / eps = +inf whichever zero an edge carries);
   * all edges tied at the current level are removed together (:254-271); every affected
     cluster then splits into the connected components of its remaining edges (:274-390);
     a component is a valid child iff it has >= minClusterSize points (minClusterSize >= 2,
@@ -53,7 +54,7 @@ def flat_labels(n, va, vb, w, min_cl_size):
         return np.zeros(max(n, 0), np.int32), 0
     va, vb, w = np.asarray(va), np.asarray(vb), np.asarray(w, np.float64)
     keep = va != vb
-    va, vb, w = va[keep], vb[keep], w[keep]
+    va, vb, w = va[keep], vb[keep], w[keep] + 0.0  # -0.0 and 0.0 are one level: +0.0, so that 1 / eps = +inf
     if va.shape[0] != n - 1:
         raise ValueError("not a spanning tree")
     adj = [dict() for _ in range(n)]  # neighbour -> edge weight

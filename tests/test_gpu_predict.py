@@ -92,7 +92,7 @@ def same_attach(got, want, where=None):
             assert bad.shape[0] == 0, (k, where, bad[:5], g[bad[:5]], w[bad[:5]])
 
 
-# every n in {1, 3, 64, 65, 1500}, m in {1, 63, 257}, d in {1, 3, 8, 9, 24}, minPts in {2, 4, 16}, every metric
+# every n in {1, 3, 64, 65, 1500}, m in {1, 63, 257}, d in {1, 3, 8, 9, 24}, minPts in {2, 4, 16} (K = KC), every metric
 ATTACH = [
     ("euclidean", "rounded_blobs", 1500, 257, 3, 4, ""),
     ("euclidean", "rounded_blobs", 65, 63, 9, 16, "dup"),
@@ -113,9 +113,19 @@ ATTACH = [
     ("pearson", "rays", 3, 1, 1, 4, ""),                     # d = 1: no variance, every distance NaN
     ("pearson", "rays", 65, 63, 3, 16, "nonfinite"),
 ]
+# K = minPts - 1 below the list capacity KC of {1, 3, 7, 15, 31}: the kernels for 7 and 31 entries, and the merge
+# kernel's "entry K - 1" pick with K < KC; minPts 32 is the largest K.  n = 65: two candidate tiles
+ATTACH_KC = [
+    ("euclidean", "rounded_blobs", 65, 63, 3, 3, ""),
+    ("cosine", "rays", 65, 63, 9, 6, ""),
+    ("euclidean", "rounded_blobs", 65, 257, 8, 20, "dup"),
+    ("cosine", "rays", 65, 63, 5, 32, ""),
+    ("euclidean", "rounded_blobs", 65, 63, 9, 6, "nonfinite"),
+    ("cosine", "rays", 9, 63, 3, 20, ""),                    # n < K < KC
+]
 
 
-@pytest.mark.parametrize("case", ATTACH, ids=lambda c: "-".join(str(x) for x in c if x != ""))
+@pytest.mark.parametrize("case", ATTACH + ATTACH_KC, ids=lambda c: "-".join(str(x) for x in c if x != ""))
 def test_attach_equals_reference(pkg, ctx, case):
     metric, family, n, m, d, min_pts, variant = case
     X, core, Q, ref = attach_case(*case)
@@ -139,7 +149,7 @@ def test_attach_equals_reference(pkg, ctx, case):
         assert np.isnan(cross_distances(Q, X, "cosine")[:, 7]).all()
 
 
-@pytest.mark.parametrize("case", [ATTACH[1], ATTACH[0], ATTACH[6], ATTACH[11], ATTACH[5]],
+@pytest.mark.parametrize("case", [ATTACH[1], ATTACH[0], ATTACH[6], ATTACH[11], ATTACH[5]] + ATTACH_KC,
                          ids=lambda c: "-".join(str(x) for x in c if x != ""))
 def test_forced_splits(pkg, ctx, case):
     """the merge kernels at small n: any split count gives the same bits"""
