@@ -61,9 +61,17 @@ __device__ __forceinline__ void wave_argmin_last(double &v, int &i) {
 }
 
 
-// Order-preserving u64 key of a non-negative MRD value (+-0 -> 0): min over keys = min value.
+// Order-preserving u64 key of any non-NaN MRD value: the sign bit set for v >= 0, every bit
+// complemented for v < 0 (cosine and Pearson weights can lie a few ulps below zero), +-0 one key.
+// min over keys = min value.  best starts at Double.MAX_VALUE and a NaN never replaces it, so no
+// NaN is keyed.
+// Integer form (every wave keys its lanes on the step's critical path): v + 0.0 turns -0.0 into
+// +0.0 and changes no other value, then the bits are flipped by the sign spread over the word,
+// with the sign bit always in it.
+constexpr unsigned long long MRD_KEY_SIGN = 0x8000000000000000ull;
 __device__ __forceinline__ unsigned long long mrd_key(double v) {
-    return v == 0.0 ? 0ull : (unsigned long long)__double_as_longlong(v);
+    const long long b = __double_as_longlong(v + 0.0);
+    return (unsigned long long)b ^ ((unsigned long long)(b >> 63) | MRD_KEY_SIGN);
 }
 
 // highest lane whose predicate holds (-1: none)
@@ -612,7 +620,7 @@ __global__ __launch_bounds__(BS) void prim_coop4_kernel(PrimIn in, int n, int se
         nnc = in.nnB[n - 1];
     }
     int cur = n - 1;
-    constexpr unsigned long long KINF = 0x7ff0000000000000ull;  // key of +inf: nothing to offer
+    constexpr unsigned long long KINF = 0x7ff0000000000000ull | MRD_KEY_SIGN;  // mrd_key(+inf): nothing to offer
     // Candidate caching: a wave's candidate changes only when one of its lanes
     // improved or its parked winner was attached in the last step, and a workgroup's only when
     // one of its waves' did -- most steps relax nothing near most waves (the sqrt-free rejection

@@ -111,10 +111,10 @@ def rays(n, d):
     return U[rng.integers(0, 6, n)] * rng.uniform(0.1, 10.0, size=(n, 1))
 
 
-def zero_row(n, d):
-    """rays with row 7 all zeros: its cosine distance to every row is NaN"""
+def zero_row(n, d, pos=7):
+    """rays with row pos (7 unless given) all zeros: its cosine distance to every row is NaN"""
     X = rays(n, d)
-    X[7] = 0.0
+    X[pos] = 0.0
     return X
 
 
