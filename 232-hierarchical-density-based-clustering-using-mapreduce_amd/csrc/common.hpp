@@ -78,7 +78,7 @@ struct hdb_ctx {
     bool boruvka_seed = true;      // seed Boruvka rounds from the previous round's edges
     int leaf_seed_k = -1;          // exact leaf: k-NN list length at least this (-1: by dimension)
     int leaf_list_rounds = 2;      // exact leaf: Boruvka rounds seeded from the k-NN lists (A/B: tools/seedk_ab.py)
-    bool boruvka_knn_seed = true;  // exact leaf: k-NN lists seed every Boruvka round
+    bool boruvka_knn_seed = true;  // exact leaf: k-NN lists seed the Boruvka rounds and bound every round's searches
     int boruvka_wave_pts = 64;     // points per scan wave (16/32/64), compacted per 512-position group
     int boruvka_early_pts = 0;     // points per scan wave in rounds < boruvka_early_rounds (0: as above)
     int boruvka_early_rounds = 5;

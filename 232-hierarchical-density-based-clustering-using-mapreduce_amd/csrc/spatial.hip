@@ -1094,9 +1094,13 @@ __global__ __launch_bounds__(256, (D <= 3 ? BOR_WPE : 1)) void boruvka_bvh_kerne
     }
 }
 
-// Work lists for the scan.  A lane searches unless its seed is exact (done) or its core
+// Work lists for the scan.  A lane searches unless its seed is exact (done) or max(core, lbw)
 // already exceeds the component bound the seeds published (it cannot supply the edge; comp_w
-// starts as all-ones bits, a NaN: no bound).  Searching lanes are compacted per group of
+// starts as all-ones bits, a NaN: no bound).  lbw is the lane's lower bound of its lightest
+// outgoing edge: what earlier scans left (their epilogue) and, with k-NN lists, what the list
+// proves this round (round_seed_kernel).  The test is strict and comp_w holds only real edges,
+// so a dropped lane can neither supply its component's edge nor tie it under (w, s, lo, hi).
+// Searching lanes are compacted per group of
 // WGRP = 512 sorted positions (one level-1 BVH node), so a wave's points stay inside one
 // small Morton range: a wave takes up to P consecutive entries of one group.
 constexpr int WGRP = 512;
@@ -1451,7 +1455,7 @@ __device__ __forceinline__ void block_publish_min(unsigned long long *arr, int32
 }
 
 // Per-round Boruvka seed.  (1) prev: round r-1's per-point best edge, when its endpoints are
-// still in different components, is a valid candidate (seed_kernel's rule).  (2) K > 0: the
+// still in different components, is a valid candidate (seed_kernel's rule).  (2) CAND: the
 // K nearest neighbours K1t found (sorted positions, squared distances): every list member
 // in another component is a valid candidate.  The lane keeps the smallest key and publishes
 // it to comp_w, so the scan starts with a component bound.  Only valid edges enter comp_w,
@@ -1460,14 +1464,26 @@ __device__ __forceinline__ void block_publish_min(unsigned long long *arr, int32
 // every such point has s' >= s_K (the list holds every point with s' < s_K), so its weight
 // is >= LB = max(fl(sqrt(s_K)), core_p); exact if w < LB, or w == LB and s < s_K.  Exact
 // lanes skip the traversal (done[i] = 1).
-template <int D, int K>
+// (3) K > 0, every round: the list as a lower bound.  cap = LB of a full list (+0.0
+// otherwise), stored once in round 0 (first).  With F the list members outside the lane's
+// component, every outgoing edge weighs >= L: a member of F at slot k weighs
+// max(fl(sqrt(s_k)), core_p, core_q), a point off the list >= cap.  CAND rounds have the
+// partners' cores loaded, so L = min(w_F, cap) with w_F the smallest such weight (+inf for an
+// empty F); the other rounds read only the K component ids, L = max(fl(sqrt(s_first)),
+// core_p) for the first (smallest s) member of F, cap for an empty F.  lbw = max(lbw, L):
+// group_compact_kernel drops the lane when that exceeds the component bound.  Once
+// lbw >= cap the list can add nothing, and a non-CAND round skips the lane's list loads.
+template <int D, int K, bool CAND>
 __global__ __launch_bounds__(256) void round_seed_kernel(const Rec<D> *__restrict__ recs, const int32_t *__restrict__ pcomp,
-                                                        int64_t n, int prev, const int32_t *__restrict__ nb_pos,
+                                                        int64_t n, int prev, int first,
+                                                        const int32_t *__restrict__ nb_pos,
                                                         const double *__restrict__ nb_s, double *__restrict__ best_w,
                                                         double *__restrict__ best_s, int32_t *__restrict__ best_lo,
                                                         int32_t *__restrict__ best_hi, int32_t *__restrict__ best_pos,
                                                         uint8_t *__restrict__ done, double *__restrict__ lbw,
-                                                        uint8_t *__restrict__ xact, unsigned long long *__restrict__ comp_w) {
+                                                        double *__restrict__ capv, uint8_t *__restrict__ xact,
+                                                        unsigned long long *__restrict__ comp_w) {
+    static_assert(K > 0 || !CAND, "candidates need a list");
     __shared__ int32_t s_c[4];
     __shared__ unsigned long long s_v[4];
     const int64_t stride = (int64_t)blockDim.x * gridDim.x;
@@ -1479,6 +1495,8 @@ __global__ __launch_bounds__(256) void round_seed_kernel(const Rec<D> *__restric
             mcomp = pcomp[i];
             int32_t bpos = -1;
             bool exact = false;
+            const double l0 = lbw[i];
+            double l = l0;
             if (prev) {
                 const double w0 = best_w[i];
                 if (w0 < INFINITY) {
@@ -1492,11 +1510,11 @@ __global__ __launch_bounds__(256) void round_seed_kernel(const Rec<D> *__restric
                     }
                 }
             }
-            if constexpr (K > 0) {
+            if constexpr (CAND) {
                 const Rec<D> &me = recs[i];
                 const double mcore = me.core;
                 const int32_t mid = me.id;
-                double sK = -INFINITY;
+                double sK = -INFINITY, wF = INFINITY;
                 bool full = true;
                 // every neighbour's component, core and id loaded up front (unconditional,
                 // clamped to the point itself): K independent random loads in flight at once
@@ -1529,6 +1547,7 @@ __global__ __launch_bounds__(256) void round_seed_kernel(const Rec<D> *__restric
                     if (mcore > mrd) mrd = mcore;
                     const double oc = ncore[k];
                     if (oc > mrd) mrd = oc;
+                    if (mrd < wF) wF = mrd;
                     const int32_t oid = nid[k];
                     const int32_t lo = mid < oid ? mid : oid, hi = mid < oid ? oid : mid;
                     if (key_less(mrd, s, lo, hi, b)) {
@@ -1536,15 +1555,62 @@ __global__ __launch_bounds__(256) void round_seed_kernel(const Rec<D> *__restric
                         bpos = j;
                     }
                 }
-                if (!exact && full && b.w < INFINITY) {
-                    double lb = sqrt(sK);
-                    if (mcore > lb) lb = mcore;
-                    exact = (b.w < lb) || (b.w == lb && b.s < sK);
+                double lb = sqrt(sK);
+                if (mcore > lb) lb = mcore;
+                if (!exact && full && b.w < INFINITY) exact = (b.w < lb) || (b.w == lb && b.s < sK);
+                double cap;
+                if (first)
+                    capv[i] = cap = full ? lb : 0.0;
+                else
+                    cap = capv[i];
+                if (full) {
+                    const double L = wF < cap ? wF : cap;
+                    if (L > l) l = L;
+                }
+            } else if constexpr (K > 0) {
+                double cap = first ? 0.0 : capv[i];
+                if (first || l < cap) {
+                    int32_t nj[K], ncomp[K];
+                    double ns[K];
+#pragma unroll
+                    for (int k = 0; k < K; k++) {
+                        nj[k] = nb_pos[i * K + k];
+                        ns[k] = nb_s[i * K + k];
+                    }
+#pragma unroll
+                    for (int k = 0; k < K; k++) ncomp[k] = pcomp[nj[k] < 0 ? i : nj[k]];
+                    const double mcore = recs[i].core;
+                    double sK = -INFINITY, sF = INFINITY;  // sF: the smallest s in F (the list ascends)
+                    bool full = true;
+#pragma unroll
+                    for (int k = 0; k < K; k++) {
+                        const double s = ns[k];
+                        if (nj[k] < 0 || !(s < INFINITY)) {
+                            full = false;
+                            continue;
+                        }
+                        sK = s > sK ? s : sK;
+                        if (ncomp[k] != mcomp && s < sF) sF = s;
+                    }
+                    if (first) {
+                        double lb = sqrt(sK);
+                        if (mcore > lb) lb = mcore;
+                        capv[i] = cap = full ? lb : 0.0;
+                    }
+                    if (full) {
+                        double L = cap;
+                        if (sF < INFINITY) {
+                            L = sqrt(sF);
+                            if (mcore > L) L = mcore;
+                        }
+                        if (L > l) l = L;
+                    }
                 }
             }
             if (done) done[i] = exact ? 1 : 0;
             xact[i] = exact ? 1 : 0;
-            if (exact && b.w > lbw[i]) lbw[i] = b.w;
+            if (exact && b.w > l) l = b.w;
+            if (l > l0) lbw[i] = l;
             best_w[i] = b.w;
             best_s[i] = b.s;
             best_lo[i] = b.lo;
@@ -1938,10 +2004,11 @@ static size_t boruvka_extra_bytes(int64_t n, bool diag) {
     return 5 * rnd(8 * per) + 5 * rnd(4 * per) + 3 * 256 + 2 * rnd(4 * per) + rnd(8 * per) +
            (diag ? rnd(8 * (size_t)BOR_STATS_REC * waves_max) : 0) +
            rnd(4 * per) + 3 * rnd(4 * (per / WGRP + 1)) + rnd(8 * waves_max) + 256 +  // + work lists
-           2 * rnd(4 * per) + rnd(8 * per) + rnd(per);  // + best_pos, pcomp, lbw, xact
+           2 * rnd(4 * per) + 2 * rnd(8 * per) + rnd(per);  // + best_pos, pcomp, lbw, cap, xact
 }
 
-// k-NN lists over the index's sorted positions (K1t with IDX): seed every Boruvka round
+// k-NN lists over the index's sorted positions (K1t with IDX): candidates of the first
+// leaf_list_rounds Boruvka rounds, lower bounds of every round (round_seed_kernel)
 struct KnnLists {
     const int32_t *pos = nullptr;
     const double *s = nullptr;  // squared distances, ascending per row
@@ -1950,7 +2017,7 @@ struct KnnLists {
 };
 
 // Boruvka rounds over a built index whose records carry the core distances.  extra: the
-// boruvka_extra_bytes(n) region.  kl (nullable): k-NN lists that seed every round.
+// boruvka_extra_bytes(n) region.  kl (nullable): k-NN lists that seed and bound the rounds.
 template <int D>
 static void boruvka_on_index(hdb_ctx *ctx, Spatial<D> &sp, int64_t n, char *extra, const KnnLists *kl,
                              int32_t *va, int32_t *vb, double *w, bool merged = false,
@@ -1965,6 +2032,7 @@ struct BoruvkaState {
     int32_t *pcomp;     // component per sorted position (a compact copy of Rec::comp)
     double *lbw;        // per point: lower bound of its best outgoing weight (monotone over rounds)
     uint8_t *xact;      // per point: best_* is the exact best of the last round
+    double *cap;        // per point: max(fl(sqrt(s_K)), core) of a full k-NN list, else +0.0 (round_seed_kernel)
 };
 template <int D>
 static BoruvkaState<D> boruvka_state(char *extra, int64_t n, size_t *used = nullptr) {
@@ -1983,6 +2051,7 @@ static BoruvkaState<D> boruvka_state(char *extra, int64_t n, size_t *used = null
     b.pcomp = ex.take<int32_t>(per);
     b.lbw = ex.take<double>(per);
     b.xact = ex.take<uint8_t>(per);
+    b.cap = ex.take<double>(per);
     if (used) *used = ex.off;
     return b;
 }
@@ -2048,23 +2117,30 @@ static void boruvka_on_index(hdb_ctx *ctx, Spatial<D> &sp, int64_t n, char *extr
         const int prev = (round > 0 && ctx->boruvka_seed) ? 1 : 0;
         // the lists stop paying once components outgrow them (their points are then all
         // inside the component): seed from them only in the first list_rounds rounds
-        const int K = (kl && round < ctx->leaf_list_rounds) ? kl->K : 0;
+        // as lower bounds they pay in every round (the further the components outgrow a
+        // list, the more its K-th distance says): the kernel runs whenever the lists exist
+        const bool cand = kl && round < ctx->leaf_list_rounds;
+        const int K = kl ? kl->K : 0;
         if (!prev && K == 0) {
             if (round > 0) hipLaunchKernelGGL(fill_inf_kernel, dim3(g), dim3(256), 0, st, best_w, n);
-            if (kl && kl->done) HIP_CHECK(hipMemsetAsync(kl->done, 0, (size_t)n, st));  // no exact seeds
             return;
         }
         // grid-stride cap (a one-lane-per-point grid measured flat, within noise; not kept)
         constexpr int SEED_MAX_BLOCKS = 2048;
         const int gs = (int)std::min<int64_t>(ceil_div(n, 256), SEED_MAX_BLOCKS);
+#define ROUND_SEED_C(KK, CC)                                                                                           \
+    hipLaunchKernelGGL((round_seed_kernel<D, KK, CC>), dim3(gs), dim3(256), 0, st, recs, pcomp, n, prev,              \
+                       round == 0 ? 1 : 0, kl ? kl->pos : nullptr, kl ? kl->s : nullptr, best_w, best_s, best_lo,      \
+                       best_hi, best_pos, kl ? kl->done : nullptr, bs.lbw, bs.cap, bs.xact, comp_w)
 #define ROUND_SEED(KK)                                                                                                 \
     case KK:                                                                                                           \
-        hipLaunchKernelGGL((round_seed_kernel<D, KK>), dim3(gs), dim3(256), 0, st, recs, pcomp, n, prev,              \
-                           kl ? kl->pos : nullptr, kl ? kl->s : nullptr, best_w, best_s, best_lo, best_hi, best_pos,  \
-                           kl ? kl->done : nullptr, bs.lbw, bs.xact, comp_w);                                          \
+        if (cand)                                                                                                      \
+            ROUND_SEED_C(KK, true);                                                                                    \
+        else                                                                                                           \
+            ROUND_SEED_C(KK, false);                                                                                   \
         break;
         switch (K) {
-            ROUND_SEED(0)
+        case 0: ROUND_SEED_C(0, false); break;
             ROUND_SEED(1)
             ROUND_SEED(3)
             ROUND_SEED(7)
@@ -2073,6 +2149,7 @@ static void boruvka_on_index(hdb_ctx *ctx, Spatial<D> &sp, int64_t n, char *extr
         default: HDB_THROW(HDB_EINVAL, "round seed: unsupported list length");
         }
 #undef ROUND_SEED
+#undef ROUND_SEED_C
         HIP_CHECK(hipGetLastError());
     };
 

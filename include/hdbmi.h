@@ -106,10 +106,14 @@ int hdb_ctx_synchronize(hdb_ctx *ctx);
  *                                  replay the sequential insertion log exactly;
  *   "boruvka_seed"    (default 1): a Boruvka round starts from the previous round's still
  *                                  valid per-point edges;
- *   "boruvka_knn_seed"(default 1): hdb_exact_mst seeds every Boruvka round from the k-NN
- *                                  lists (lanes whose seed is provably exact skip the scan);
+ *   "boruvka_knn_seed"(default 1): hdb_exact_mst keeps the k-NN lists for its Boruvka rounds:
+ *                                  as seeds (lanes whose seed is provably exact skip the scan)
+ *                                  and, in every round, as lower bounds (a lane whose list
+ *                                  proves every outgoing edge heavier than its component's
+ *                                  bound skips the scan); 0: no lists, neither;
  *                                  "leaf_seed_k" (list length, -1: by dimension),
- *                                  "leaf_list_rounds" (default 2: rounds seeded from the lists);
+ *                                  "leaf_list_rounds" (default 2: rounds whose list members are
+ *                                  candidate edges; the lower bound runs in every round);
  *   "boruvka_wave_pts" (default 64; 16/32/64): points per scan wave; "boruvka_early_pts" /
  *                                  "boruvka_early_rounds": another size for the first rounds;
  *   "boruvka_adj_seed"(default 1): Morton-adjacent pairs across components bound every
