@@ -300,22 +300,11 @@ __global__ void att_fill_kernel(double *__restrict__ core_q, double cv, int32_t 
     }
 }
 
-struct ACarve {
-    char *base = nullptr;
-    size_t off = 0;
-    template <class T>
-    T *take(size_t count) {
-        const size_t o = off;
-        off += (sizeof(T) * std::max<size_t>(count, 1) + 255) & ~size_t(255);
-        return base ? (T *)(base + o) : nullptr;
-    }
-};
-
 struct AttState {
     double *Xp, *xnrm, *xcore, *Qp, *qnrm, *cq, *plist, *pw, *ps;
     int32_t *pj;
 };
-AttState att_carve(ACarve &cv, int64_t n, int64_t npad, int64_t m, int dp, int splits, int KC, bool own_cq) {
+AttState att_carve(Carver &cv, int64_t n, int64_t npad, int64_t m, int dp, int splits, int KC, bool own_cq) {
     AttState s;
     s.Xp = cv.take<double>((size_t)npad * dp);
     s.xnrm = cv.take<double>((size_t)n);
@@ -375,11 +364,8 @@ void attach_points_device(hdb_ctx *ctx, const double *X, int64_t n, int d, const
     }
     const int dp = (int)(ceil_div(d, ATT_DC) * ATT_DC);
     const int64_t tps = ceil_div(ntiles, splits);  // tiles per split; the last splits may be empty
-    ACarve sz;
-    att_carve(sz, n, npad, m, dp, (int)splits, KC, core_q == nullptr);
-    ACarve cv;
-    cv.base = (char *)arena(ctx, A_WORK0, sz.off);
-    const AttState s = att_carve(cv, n, npad, m, dp, (int)splits, KC, core_q == nullptr);
+    const AttState s =
+        carve(ctx, A_WORK0, [&](Carver &cv) { return att_carve(cv, n, npad, m, dp, (int)splits, KC, core_q == nullptr); });
     double *cq = core_q ? core_q : s.cq;
     const int gn = (int)std::min<int64_t>(ceil_div(n, 256), 4096);
     if (npad > n) HIP_CHECK(hipMemsetAsync(s.Xp + (size_t)n * dp, 0, sizeof(double) * (size_t)(npad - n) * dp, st));

@@ -432,17 +432,6 @@ __global__ void gen_out_kernel(const int32_t *__restrict__ perm, const int32_t *
     }
 }
 
-struct GCarve {
-    char *base = nullptr;
-    size_t off = 0;
-    template <class T>
-    T *take(size_t count) {
-        const size_t o = off;
-        off += (sizeof(T) * std::max<size_t>(count, 1) + 255) & ~size_t(255);
-        return base ? (T *)(base + o) : nullptr;
-    }
-};
-
 struct GenState {
     double *Xg, *gcore, *gnrm, *tmin, *best_w, *best_s, *win_w, *ew;
     int32_t *gcomp, *gid, *ttag, *comp, *base_order, *order, *best_lo, *best_hi, *parent, *parent2, *ea, *eb, *p1, *p2;
@@ -450,7 +439,7 @@ struct GenState {
     uint64_t *k1, *k2;
     uint32_t *ck1, *ck2;
 };
-GenState gen_carve(GCarve &cv, int64_t n, int64_t npad, int dp, int64_t ntiles) {
+GenState gen_carve(Carver &cv, int64_t n, int64_t npad, int dp, int64_t ntiles) {
     const size_t per = (size_t)n;
     GenState s;
     s.Xg = cv.take<double>((size_t)npad * dp);
@@ -515,22 +504,15 @@ void boruvka_generic_device(hdb_ctx *ctx, const double *X, int64_t n, int d, con
     hipStream_t st = ctx->stream;
     const int dp = (int)(ceil_div(d, GEN_DC) * GEN_DC);
     const int64_t ntiles = ceil_div(n, (int64_t)GEN_CT), npad = ntiles * GEN_CT;
-    GCarve sz;
-    gen_carve(sz, n, npad, dp, ntiles);
-    GCarve cv;
-    cv.base = (char *)arena(ctx, A_WORK0, sz.off);
-    const GenState s = gen_carve(cv, n, npad, dp, ntiles);
+    const GenState s = carve(ctx, A_WORK0, [&](Carver &cv) { return gen_carve(cv, n, npad, dp, ntiles); });
     const size_t per = (size_t)n;
     unsigned long long *comp_w = s.comp3, *comp_s = s.comp3 + per, *comp_key = s.comp3 + 2 * per;
     int B = 1;  // bits of a component id (the sort key carries one more: the seeded flag)
     while (B < 31 && ((int64_t)1 << B) < n) B++;
-    // one radix scratch for the three sorts (the arena may move when it grows)
-    size_t tb_core = 0, tb_comp = 0, tb_id = 0;
-    HIP_CHECK(sort_pairs(nullptr, tb_core, s.k1, s.k2, s.p1, s.base_order, n, 0, 64, st));
-    HIP_CHECK(sort_pairs(nullptr, tb_comp, s.ck1, s.ck2, s.base_order, s.order, n, 0, B + 1, st));
-    HIP_CHECK(sort_pairs(nullptr, tb_id, s.k1, s.k2, s.p1, s.p2, n - 1, 0, 64, st));
-    const size_t tb_max = std::max(tb_core, std::max(tb_comp, tb_id));
-    void *tmp = arena(ctx, A_SORT, tb_max);
+    // one radix scratch sized for the three sorts up front: the arena synchronises the stream when it
+    // grows, which the round loop (one round in flight) must not do
+    arena(ctx, A_SORT, std::max({sort_pairs_bytes<uint64_t, int32_t>(n, 0, 64), sort_pairs_bytes<uint32_t, int32_t>(n, 0, B + 1),
+                                 sort_pairs_bytes<uint64_t, int32_t>(n - 1, 0, 64)}));
 
     const int g = (int)std::min<int64_t>(ceil_div(n, 256), 4096);
     const int gt = (int)std::min<int64_t>(ceil_div(ntiles, 256), 4096);
@@ -540,8 +522,7 @@ void boruvka_generic_device(hdb_ctx *ctx, const double *X, int64_t n, int d, con
     // every point its own component; the base order: ids by ascending core distance
     hipLaunchKernelGGL(gen_iota_kernel, dim3(g), dim3(256), 0, st, s.comp, s.p1, n);
     hipLaunchKernelGGL(gen_corekey_kernel, dim3(g), dim3(256), 0, st, core, n, s.k1);
-    size_t tb = tb_max;
-    HIP_CHECK(sort_pairs(tmp, tb, s.k1, s.k2, s.p1, s.base_order, n, 0, 64, st));
+    sort_pairs(ctx, A_SORT, s.k1, s.k2, s.p1, s.base_order, n, 0, 64);
     HIP_CHECK(hipGetLastError());
 
     int64_t *hcnt = pinned_words(ctx);
@@ -565,8 +546,7 @@ void boruvka_generic_device(hdb_ctx *ctx, const double *X, int64_t n, int d, con
         if (round > 0) {
             hipLaunchKernelGGL(gen_compkey_kernel, dim3(g), dim3(256), 0, st, s.comp, s.base_order, n, s.best_lo,
                                s.best_hi, s.ck1);
-            tb = tb_max;
-            HIP_CHECK(sort_pairs(tmp, tb, s.ck1, s.ck2, s.base_order, s.order, n, 0, B + 1, st));
+            sort_pairs(ctx, A_SORT, s.ck1, s.ck2, s.base_order, s.order, n, 0, B + 1);
             order = s.order;
         }
         hipLaunchKernelGGL(gen_gather_kernel, dim3(g), dim3(256), 0, st, X, n, d, dp, metric, order, core, s.comp, s.Xg,
@@ -648,11 +628,9 @@ void boruvka_generic_device(hdb_ctx *ctx, const double *X, int64_t n, int d, con
     }
     const int64_t ne = n - 1;
     hipLaunchKernelGGL(gen_idkey_kernel, dim3(g), dim3(256), 0, st, s.ea, s.eb, ne, s.k1, s.p1);
-    tb = tb_max;
-    HIP_CHECK(sort_pairs(tmp, tb, s.k1, s.k2, s.p1, s.p2, ne, 0, 64, st));
+    sort_pairs(ctx, A_SORT, s.k1, s.k2, s.p1, s.p2, ne, 0, 64);
     hipLaunchKernelGGL(gen_wkey_kernel, dim3(g), dim3(256), 0, st, s.p2, s.ew, ne, s.k1);
-    tb = tb_max;
-    HIP_CHECK(sort_pairs(tmp, tb, s.k1, s.k2, s.p2, s.p1, ne, 0, 64, st));
+    sort_pairs(ctx, A_SORT, s.k1, s.k2, s.p2, s.p1, ne, 0, 64);
     hipLaunchKernelGGL(gen_out_kernel, dim3(g), dim3(256), 0, st, s.p1, s.ea, s.eb, s.ew, ne, va, vb, w);
     HIP_CHECK(hipGetLastError());
 }

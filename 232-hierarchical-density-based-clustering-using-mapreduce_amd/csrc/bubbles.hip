@@ -18,6 +18,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "sort.hpp"
 
 namespace hdb {
 
@@ -184,20 +185,15 @@ void bubble_stats_device(hdb_ctx *ctx, const double *X, int64_t n, int d, const 
                          double *ls, double *ss, double *rep, double *info) {
     if (nb <= 0) return;
     if (n > INT32_MAX) HDB_THROW(HDB_EINVAL, "n exceeds int32");
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        size_t o = off;
-        off += (bytes + 255) & ~size_t(255);
-        return o;
-    };
-    size_t o_keys = carve(sizeof(int32_t) * (n + 1)), o_perm = carve(sizeof(int32_t) * (n + 1)),
-           o_iota = carve(sizeof(int32_t) * (n + 1)), o_cnt = carve(sizeof(int32_t) * (nb + 1)),
-           o_off = carve(sizeof(int64_t) * (nb + 1)), o_bad = carve(sizeof(int));
-    char *base = (char *)arena(ctx, A_WORK0, off);
-    int32_t *keys = (int32_t *)(base + o_keys), *perm = (int32_t *)(base + o_perm), *iota = (int32_t *)(base + o_iota);
-    int32_t *cnt = (int32_t *)(base + o_cnt);
-    int64_t *offs = (int64_t *)(base + o_off);
-    int *bad = (int *)(base + o_bad);
+    int32_t *keys, *perm, *iota, *cnt;
+    int64_t *offs;
+    int *bad;
+    carve(ctx, A_WORK0, [&](Carver &cv) {
+        keys = cv.take<int32_t>(n + 1), perm = cv.take<int32_t>(n + 1), iota = cv.take<int32_t>(n + 1);
+        cnt = cv.take<int32_t>(nb + 1);
+        offs = cv.take<int64_t>(nb + 1);
+        bad = cv.take<int>(1);
+    });
     int g = 2048;
     HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(int32_t) * (nb + 1), ctx->stream));
     HIP_CHECK(hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
@@ -205,20 +201,16 @@ void bubble_stats_device(hdb_ctx *ctx, const double *X, int64_t n, int d, const 
     if (n > 0) {
         hipLaunchKernelGGL(iota32_kernel, dim3(g), dim3(256), 0, ctx->stream, iota, n);
         hipLaunchKernelGGL(bubble_count_kernel, dim3(g), dim3(256), 0, ctx->stream, bo, n, nb, cnt, bad);
-        size_t tb = 0;
         int end_bit = 1;
         while (end_bit < 32 && (int64_t(1) << end_bit) < nb) end_bit++;
-        HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, bo, keys, iota, perm, (int)n, 0, end_bit, ctx->stream));
-        void *tmp = arena(ctx, A_SORT, tb);
-        HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, bo, keys, iota, perm, (int)n, 0, end_bit, ctx->stream));
+        with_tmp(ctx, A_SORT, [&](void *tmp, size_t &tb) {
+            return hipcub::DeviceRadixSort::SortPairs(tmp, tb, bo, keys, iota, perm, (int)n, 0, end_bit, ctx->stream);
+        });
     }
     // exclusive scan of counts (int32) into int64 offsets
-    {
-        size_t tb = 0;
-        HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cnt, offs, (int)(nb + 1), ctx->stream));
-        void *tmp = arena(ctx, A_SORT, tb);
-        HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, offs, (int)(nb + 1), ctx->stream));
-    }
+    with_tmp(ctx, A_SORT, [&](void *tmp, size_t &tb) {
+        return hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, offs, (int)(nb + 1), ctx->stream);
+    });
     if (ctx->bubble_fold_dim) {
         hipLaunchKernelGGL(bubble_fold_dim_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(nb * d, 256), 16384)),
                            dim3(256), 0, ctx->stream, X, d, perm, offs, nb, ls, ss);
@@ -307,20 +299,16 @@ void bubble_partials_device(hdb_ctx *ctx, const double *X, int64_t n, int d, con
     SliceCuts sc{};
     for (int s = 0; s <= S; s++) sc.c[s] = h_cuts[s];
     sc.S = S;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        size_t o = off;
-        off += (bytes + 255) & ~size_t(255);
-        return o;
-    };
-    size_t o_key = carve(sizeof(int32_t) * (n + 1)), o_skey = carve(sizeof(int32_t) * (n + 1)),
-           o_perm = carve(sizeof(int32_t) * (n + 1)), o_iota = carve(sizeof(int32_t) * (n + 1)),
-           o_cnt = carve(sizeof(int32_t) * (m + 1)), o_off = carve(sizeof(int64_t) * (m + 1)), o_bad = carve(sizeof(int));
-    char *base = (char *)arena(ctx, A_WORK0, off);
-    int32_t *key = (int32_t *)(base + o_key), *skey = (int32_t *)(base + o_skey), *perm = (int32_t *)(base + o_perm),
-            *iota = (int32_t *)(base + o_iota), *cnt = (int32_t *)(base + o_cnt);
-    int64_t *offs = (int64_t *)(base + o_off);
-    int *bad = (int *)(base + o_bad);
+    int32_t *key, *skey, *perm, *iota, *cnt;
+    int64_t *offs;
+    int *bad;
+    carve(ctx, A_WORK0, [&](Carver &cv) {
+        key = cv.take<int32_t>(n + 1), skey = cv.take<int32_t>(n + 1);
+        perm = cv.take<int32_t>(n + 1), iota = cv.take<int32_t>(n + 1);
+        cnt = cv.take<int32_t>(m + 1);
+        offs = cv.take<int64_t>(m + 1);
+        bad = cv.take<int>(1);
+    });
     const int g = 2048;
     HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(int32_t) * (m + 1), ctx->stream));
     HIP_CHECK(hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
@@ -330,17 +318,13 @@ void bubble_partials_device(hdb_ctx *ctx, const double *X, int64_t n, int d, con
         hipLaunchKernelGGL(slice_key_kernel, dim3(g), dim3(256), 0, ctx->stream, bo, n, nb, sc, key, cnt, bad);
         int end_bit = 1;
         while (end_bit < 32 && (int64_t(1) << end_bit) < m) end_bit++;
-        size_t tb = 0;
-        HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, key, skey, iota, perm, (int)n, 0, end_bit, ctx->stream));
-        void *tmp = arena(ctx, A_SORT, tb);
-        HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, key, skey, iota, perm, (int)n, 0, end_bit, ctx->stream));
+        with_tmp(ctx, A_SORT, [&](void *tmp, size_t &tb) {
+            return hipcub::DeviceRadixSort::SortPairs(tmp, tb, key, skey, iota, perm, (int)n, 0, end_bit, ctx->stream);
+        });
     }
-    {
-        size_t tb = 0;
-        HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cnt, offs, (int)(m + 1), ctx->stream));
-        void *tmp = arena(ctx, A_SORT, tb);
-        HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, offs, (int)(m + 1), ctx->stream));
-    }
+    with_tmp(ctx, A_SORT, [&](void *tmp, size_t &tb) {
+        return hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, offs, (int)(m + 1), ctx->stream);
+    });
     // a (slice, bubble) segment is a slice's members of the bubble in row order: K4's fold
     hipLaunchKernelGGL(bubble_fold_dim_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(m * d, 256), 16384)), dim3(256),
                        0, ctx->stream, X, d, perm, offs, m, pls, pss);

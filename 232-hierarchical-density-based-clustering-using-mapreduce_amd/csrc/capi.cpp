@@ -199,8 +199,12 @@ int hdb_leaf_msts(hdb_ctx *ctx, const double *X, const int64_t *offsets, int32_t
             HIP_CHECK(hipMemsetAsync(dcore, 0, sizeof(double) * std::max<int64_t>(n, 0), ctx->stream));
         } else {
             // offsets + small list on device
-            int64_t *d_off = (int64_t *)arena(ctx, A_STAGE_IN, sizeof(int64_t) * (P + 1) + sizeof(int32_t) * (P + 1) + 256);
-            int32_t *d_parts = (int32_t *)((char *)d_off + ((sizeof(int64_t) * (P + 1) + 255) & ~size_t(255)));
+            int64_t *d_off;
+            int32_t *d_parts;
+            carve(ctx, A_STAGE_IN, [&](Carver &cv) {
+                d_off = cv.take<int64_t>(P + 1);
+                d_parts = cv.take<int32_t>(P + 1);
+            });
             HIP_CHECK(hipMemcpyAsync(d_off, offs.data(), sizeof(int64_t) * (P + 1), hipMemcpyHostToDevice, ctx->stream));
             if (!small.empty())
                 HIP_CHECK(hipMemcpyAsync(d_parts, small.data(), sizeof(int32_t) * small.size(), hipMemcpyHostToDevice,

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
@@ -122,6 +123,33 @@ enum {
 };
 
 void *arena(hdb_ctx *ctx, int slot, size_t bytes);
+
+// Device scratch layout.  Every arena is handed out by one bump carver, and every layout is written once,
+// as a function of a Carver: carve() runs it on a null base to size the arena, then on the real base to
+// assign the pointers, so the size and the pointers cannot disagree.  take() rounds every array up to 256
+// bytes and never takes less than one element.  An array's offset follows from the takes before it alone:
+// a site that keeps the order and counts of its takes keeps every offset, and the arena's total is their
+// sum with no hand-kept reserve on top (totals may change when a layout changes, offsets of the arrays
+// before the change do not).  Two names over one take are deliberate aliases (lifetimes that do not
+// overlap) and carry a comment where they are made.
+struct Carver {
+    char *base = nullptr;
+    size_t off = 0;
+    template <class T>
+    T *take(int64_t count) {
+        T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
+        off += ((size_t)std::max<int64_t>(count, 1) * sizeof(T) + 255) & ~size_t(255);
+        return p;
+    }
+};
+template <class F>
+inline auto carve(hdb_ctx *ctx, int slot, F &&layout) {
+    Carver probe;
+    layout(probe);
+    Carver cv{(char *)arena(ctx, slot, probe.off)};
+    return layout(cv);
+}
+
 constexpr int PINNED_WORDS = 512;
 int64_t *pinned_words(hdb_ctx *ctx);
 // grow-only pinned host buffer (synchronises the stream before it grows)
@@ -324,6 +352,8 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long x)
 }
 
 __host__ __device__ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// blocks of 256 threads over `count` items, capped for grid-stride kernels
+inline int grid_for(int64_t count) { return (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(count, 256), 16384)); }
 
 // grid-stride helper
 #define HDB_GRID_STRIDE(i, n)                                                                   \

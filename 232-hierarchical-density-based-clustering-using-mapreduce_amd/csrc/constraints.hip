@@ -293,19 +293,6 @@ __global__ void cs_labels(const int32_t *__restrict__ point_cluster, int64_t n, 
     cs_flag(err, e);
 }
 
-inline int grid_for(int64_t count) { return (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(count, 256), 16384)); }
-
-struct Carver {
-    char *base = nullptr;
-    size_t off = 0;
-    template <class T>
-    T *take(int64_t count) {
-        size_t o = off;
-        off += ((size_t)std::max<int64_t>(count, 1) * sizeof(T) + 255) & ~size_t(255);
-        return base ? (T *)(base + o) : nullptr;
-    }
-};
-
 }  // namespace
 
 void constrained_flat_labels_device(hdb_ctx *ctx, const int32_t *parent, const double *stability,
@@ -328,7 +315,6 @@ void constrained_flat_labels_device(hdb_ctx *ctx, const int32_t *parent, const d
     while ((int64_t(1) << J) < K) J++;  // 2^J >= K > the deepest chain
     const int64_t stride = K + 1;
     // temporary memory, sized once from K (n and m are only read): one zero-filled block first
-    Carver probe;
     int32_t *zero = nullptr, *nch = nullptr, *arrive = nullptr, *anc = nullptr, *dep[2] = {}, *off = nullptr,
             *kids = nullptr, *sval = nullptr, *self = nullptr, *top = nullptr, *flab = nullptr, *val1 = nullptr,
             *val2 = nullptr;
@@ -338,7 +324,7 @@ void constrained_flat_labels_device(hdb_ctx *ctx, const int32_t *parent, const d
     CMeta *meta = nullptr;
     int32_t *pnch = nullptr;
     size_t zero_bytes = 0;
-    auto layout = [&](Carver &cv) {
+    carve(ctx, A_FLAT1, [&](Carver &cv) {
         zero = cv.take<int32_t>(64);  // [0] error bits, [1] selected clusters
         nch = cv.take<int32_t>(stride);
         arrive = cv.take<int32_t>(stride);
@@ -357,10 +343,7 @@ void constrained_flat_labels_device(hdb_ctx *ctx, const int32_t *parent, const d
         jp[0] = cv.take<unsigned long long>(stride), jp[1] = cv.take<unsigned long long>(stride);
         key1 = cv.take<unsigned long long>(K), key2 = cv.take<unsigned long long>(K);
         val1 = cv.take<int32_t>(K), val2 = cv.take<int32_t>(K);
-    };
-    layout(probe);
-    Carver cv{(char *)arena(ctx, A_FLAT1, probe.off), 0};
-    layout(cv);
+    });
     int *err = zero;
     int32_t *count = zero + 1;
     HIP_CHECK(hipMemsetAsync(zero, 0, zero_bytes, st));
@@ -389,12 +372,9 @@ void constrained_flat_labels_device(hdb_ctx *ctx, const int32_t *parent, const d
     {
         int kb = 1;
         while ((int64_t(1) << kb) <= K) kb++;
-        size_t tb = 0, tb2 = 0;
-        HIP_CHECK(sort_pairs(nullptr, tb, skey1, skey2, sval, kids, K, 0, kb, st));
-        HIP_CHECK(rocprim::exclusive_scan(nullptr, tb2, nch, off, 0, (size_t)stride, rocprim::plus<int32_t>(), st));
-        void *tmp = arena(ctx, A_FLAT_TMP, std::max(tb, tb2));
-        HIP_CHECK(sort_pairs(tmp, tb, skey1, skey2, sval, kids, K, 0, kb, st));
-        HIP_CHECK(rocprim::exclusive_scan(tmp, tb2, nch, off, 0, (size_t)stride, rocprim::plus<int32_t>(), st));
+        // (both take A_FLAT_TMP in turn; the arena only grows, so from the second call on neither request moves it)
+        sort_pairs(ctx, A_FLAT_TMP, skey1, skey2, sval, kids, K, 0, kb);
+        exclusive_sum(ctx, A_FLAT_TMP, nch, off, stride);
         hipLaunchKernelGGL(cs_meta, dim3(grid_for(K)), dim3(CS_TB), 0, st, anc, nch, off, kids, K32, meta, pnch);
     }
     // 4. the bottom-up pass, one launch: at most one workgroup per CU
@@ -409,12 +389,7 @@ void constrained_flat_labels_device(hdb_ctx *ctx, const int32_t *parent, const d
         hipLaunchKernelGGL(cs_jump, dim3(gk), dim3(CS_TB), 0, st, jp[j & 1], jp[(j + 1) & 1], K32);
     hipLaunchKernelGGL(cs_sel_keys, dim3(grid_for(K)), dim3(CS_TB), 0, st, jp[J & 1], min_id, K32, key1, val1, top,
                        count);
-    {
-        size_t tb = 0;
-        HIP_CHECK(sort_pairs(nullptr, tb, key1, key2, val1, val2, K, 0, 64, st));
-        void *tmp = arena(ctx, A_FLAT_TMP, tb);
-        HIP_CHECK(sort_pairs(tmp, tb, key1, key2, val1, val2, K, 0, 64, st));
-    }
+    sort_pairs(ctx, A_FLAT_TMP, key1, key2, val1, val2, K, 0, 64);
     hipLaunchKernelGGL(cs_number, dim3(grid_for(K)), dim3(CS_TB), 0, st, key2, val2, K32, flab, o.flat_label);
     next_part("cfl_labels");
     if (n > 0)

@@ -2043,18 +2043,12 @@ __global__ __launch_bounds__(256) void pr_walk(const int32_t *__restrict__ anc, 
 // each: 24m bytes, so the u64 array after them is 8-byte aligned), hkey (m u64), 192 jump flags
 inline size_t fz_layout(int64_t m) { return (size_t)m * 24 + (size_t)m * 8 + 192 * 4; }
 
-inline int grid_for(int64_t count) { return (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(count, 256), 16384)); }
-
-struct Carver {
-    char *base = nullptr;
-    size_t off = 0;
-    template <class T>
-    T *take(int64_t count) {
-        size_t o = off;
-        off += ((size_t)std::max<int64_t>(count, 1) * sizeof(T) + 255) & ~size_t(255);
-        return base ? (T *)(base + o) : nullptr;
-    }
-};
+// the device error word of K6, read back on the host (sections 5 and 7)
+void throw_tree_errors(int e) {
+    if (e & FE_CYCLE) HDB_THROW(HDB_EINVAL, "flat labels: the edges contain a cycle");
+    if (e & FE_ROOTS) HDB_THROW(HDB_EINVAL, "flat labels: the edges are not a spanning tree");
+    if (e & FE_JUMP) HDB_THROW(HDB_EDEVICE, "flat labels: pointer jumping did not converge in its launch budget");
+}
 
 }  // namespace
 
@@ -2084,45 +2078,29 @@ static void flat_device_impl(hdb_ctx *ctx, const int32_t *va, const int32_t *vb,
     const int64_t nv = relabel ? 2 * mm : n;
 
     // scratch: sizes are fixed by n and ne
-    auto layout = [&](Carver &cv) {
-        cv.take<int32_t>(ne);            // keep
-        cv.take<int32_t>(ne);            // pos
-        cv.take<int32_t>(mm);            // ca
-        cv.take<int32_t>(mm);            // cb
-        cv.take<double>(mm);             // cw
-        cv.take<int64_t>(4);             // m_dev, err, flags
-        cv.take<int32_t>(mm);            // ea
-        cv.take<int32_t>(mm);            // eb
-        cv.take<double>(mm);             // ew
-        cv.take<int32_t>(2 * mm);        // lab
-        cv.take<LRec>(nv + mm);          // label records
-        cv.take<int32_t>(nv + mm);       // stamp
-        cv.take<int32_t>(nv);            // orig (relabelled vertices)
-        cv.take<int32_t>(mm);            // hooked
-        for (int k = 0; k < 3; k++) cv.take<int32_t>(mm);      // parent esize eminid
-        cv.take<int32_t>(n);             // pparent
-    };
-    Carver probe;
-    layout(probe);
-    Carver cv{(char *)arena(ctx, A_FLAT0, probe.off), 0};
-    int32_t *keep = cv.take<int32_t>(ne), *pos = cv.take<int32_t>(ne);
-    int32_t *ca = cv.take<int32_t>(mm), *cb = cv.take<int32_t>(mm);
-    double *cw = cv.take<double>(mm);
-    int64_t *words = cv.take<int64_t>(4);
+    int32_t *keep, *pos, *ca, *cb, *ea, *eb, *orig, *pparent;
+    double *cw, *ew;
+    int64_t *words;
+    DC dc;
+    carve(ctx, A_FLAT0, [&](Carver &cv) {
+        keep = cv.take<int32_t>(ne), pos = cv.take<int32_t>(ne);
+        ca = cv.take<int32_t>(mm), cb = cv.take<int32_t>(mm);
+        cw = cv.take<double>(mm);
+        words = cv.take<int64_t>(4);  // m_dev, err, flags, the cluster count
+        ea = cv.take<int32_t>(mm), eb = cv.take<int32_t>(mm);
+        ew = cv.take<double>(mm);
+        dc.lab = cv.take<int32_t>(2 * mm);
+        dc.lr = cv.take<LRec>(nv + mm);
+        dc.stamp = cv.take<int32_t>(nv + mm);
+        orig = cv.take<int32_t>(nv);  // relabelled vertices
+        dc.hooked = cv.take<int32_t>(mm);
+        dc.parent = cv.take<int32_t>(mm);
+        dc.esize = cv.take<int32_t>(mm);
+        dc.eminid = cv.take<int32_t>(mm);
+        pparent = cv.take<int32_t>(n);
+    });
     int64_t *m_dev = words;
     int *err = (int *)(words + 1), *flags = (int *)(words + 2);
-    int32_t *ea = cv.take<int32_t>(mm), *eb = cv.take<int32_t>(mm);
-    double *ew = cv.take<double>(mm);
-    DC dc;
-    dc.lab = cv.take<int32_t>(2 * mm);
-    dc.lr = cv.take<LRec>(nv + mm);
-    dc.stamp = cv.take<int32_t>(nv + mm);
-    int32_t *orig = cv.take<int32_t>(nv);
-    dc.hooked = cv.take<int32_t>(mm);
-    dc.parent = cv.take<int32_t>(mm);
-    dc.esize = cv.take<int32_t>(mm);
-    dc.eminid = cv.take<int32_t>(mm);
-    int32_t *pparent = cv.take<int32_t>(n);
     dc.n = nv;
     dc.m = m;
     dc.orig = relabel ? orig : nullptr;
@@ -2132,10 +2110,7 @@ static void flat_device_impl(hdb_ctx *ctx, const int32_t *va, const int32_t *vb,
     if (ne > 0) {
         if (ne > INT32_MAX) HDB_THROW(HDB_EINVAL, "too many edges");
         hipLaunchKernelGGL(fl_mark, dim3(grid_for(ne)), dim3(256), 0, st, va, vb, w, ne, n, keep, err);
-        size_t tb = 0;
-        HIP_CHECK(rocprim::exclusive_scan(nullptr, tb, keep, pos, 0, (size_t)ne, rocprim::plus<int32_t>(), st));
-        void *tmp = arena(ctx, A_FLAT_TMP, tb);
-        HIP_CHECK(rocprim::exclusive_scan(tmp, tb, keep, pos, 0, (size_t)ne, rocprim::plus<int32_t>(), st));
+        exclusive_sum(ctx, A_FLAT_TMP, keep, pos, ne);
         hipLaunchKernelGGL(fl_compact, dim3(grid_for(ne)), dim3(256), 0, st, va, vb, w, ne, keep, pos, m, ca, cb, cw,
                            m_dev);
         // a descending list sets bit 1 in every workgroup: few workgroups, few same-address atomics
@@ -2167,19 +2142,14 @@ static void flat_device_impl(hdb_ctx *ctx, const int32_t *va, const int32_t *vb,
     const int32_t *perm = nullptr;
     int desc = !(order & 1);
     if (desc == 0 && (order & 2)) {  // neither ascending nor descending: radix sort by weight
-        Carver sp;
-        sp.take<double>(m);
-        sp.take<double>(m);
-        sp.take<int32_t>(m);
-        sp.take<int32_t>(m);
-        Carver sc{(char *)arena(ctx, A_FLAT1, sp.off), 0};
-        double *k1 = sc.take<double>(m), *k2 = sc.take<double>(m);
-        int32_t *i1 = sc.take<int32_t>(m), *i2 = sc.take<int32_t>(m);
+        double *k1, *k2;
+        int32_t *i1, *i2;
+        carve(ctx, A_FLAT1, [&](Carver &cv) {
+            k1 = cv.take<double>(m), k2 = cv.take<double>(m);
+            i1 = cv.take<int32_t>(m), i2 = cv.take<int32_t>(m);
+        });
         hipLaunchKernelGGL(fl_sort_keys, dim3(g), dim3(256), 0, st, cw, m, k1, i1);
-        size_t tb = 0;
-        HIP_CHECK(sort_pairs(nullptr, tb, k1, k2, i1, i2, m, 0, 64, st));
-        void *tmp = arena(ctx, A_FLAT_TMP, tb);
-        HIP_CHECK(sort_pairs(tmp, tb, k1, k2, i1, i2, m, 0, 64, st));
+        sort_pairs(ctx, A_FLAT_TMP, k1, k2, i1, i2, m, 0, 64);
         perm = i2;
     }
     hipLaunchKernelGGL(fl_rank, dim3(g), dim3(256), 0, st, ca, cb, cw, m, desc, perm, ea, eb, ew, dc.lab, dc.parent);
@@ -2240,49 +2210,38 @@ static void flat_device_impl(hdb_ctx *ctx, const int32_t *va, const int32_t *vb,
     // reuse the union-find scratch (n + m ints each) for the node arrays
     int32_t *top = (int32_t *)dc.lr, *pnode = top + (n + m), *nvalid = pnode + (n + m), *vsum = nvalid + (n + m),
             *is_start = dc.stamp;
-    Carver nc2{nullptr, 0};
-    nc2.take<int32_t>(m);  // cup / cs
-    nc2.take<int32_t>(m);  // cid
-    nc2.take<uint64_t>(m);
-    nc2.take<uint64_t>(m);
-    nc2.take<double>(m);
-    nc2.take<double>(m);
-    nc2.take<int32_t>(m);  // seg
-    nc2.take<double>(m);   // stab
-    nc2.take<int32_t>(m);  // cpar
-    nc2.take<int32_t>(m);  // cminid
-    nc2.take<int32_t>(m);  // clab
-    nc2.take<int32_t>(64);  // jump flags
-    nc2.take<int64_t>(1);  // cluster count
-    for (int k = 0; k < 11; k++) nc2.take<int32_t>(m);  // csz kstart kids pnodes poff ssel Kp rc rl mlist llist
-    for (int k = 0; k < 7; k++) nc2.take<uint64_t>(m);  // jw tw cpv lw rs mpre postv
-    nc2.take<char>(fz_layout(m));                        // zeroed block
-    nc2.take<int32_t>(n);                                // mk
-    nc2.take<int32_t>(n);                                // rk
-    Carver cv2{(char *)arena(ctx, A_FLAT1, nc2.off), 0};
-    int32_t *cs = cv2.take<int32_t>(m), *cid = cv2.take<int32_t>(m);
-    uint64_t *key1 = cv2.take<uint64_t>(m), *key2 = cv2.take<uint64_t>(m);
-    double *val1 = cv2.take<double>(m), *val2 = cv2.take<double>(m);
-    int32_t *seg = cv2.take<int32_t>(m);
-    double *stab = cv2.take<double>(m);
-    int32_t *cpar = cv2.take<int32_t>(m), *cminid = cv2.take<int32_t>(m), *clab = cv2.take<int32_t>(m);
-    int *jflags = cv2.take<int32_t>(64);
-    unsigned long long *groot = (unsigned long long *)cv2.take<int64_t>(1);  // outlier scores: the root's eps_max
-    int32_t *csz = cv2.take<int32_t>(m), *kstart = cv2.take<int32_t>(m), *kids = cv2.take<int32_t>(m),
-            *pnodes = cv2.take<int32_t>(m), *poff = cv2.take<int32_t>(m),
-            *ssel = cv2.take<int32_t>(m), *Kp = cv2.take<int32_t>(m), *rc = cv2.take<int32_t>(m),
-            *rl = cv2.take<int32_t>(m), *mlist = cv2.take<int32_t>(m), *llist = cv2.take<int32_t>(m);
-    uint64_t *jw = cv2.take<uint64_t>(m), *tw = cv2.take<uint64_t>(m);
-    double *cpv = cv2.take<double>(m);
-    uint64_t *lw = cv2.take<uint64_t>(m);
-    double *rs = cv2.take<double>(m), *mpre = cv2.take<double>(m), *postv = cv2.take<double>(m);
-    char *fz = cv2.take<char>(fz_layout(m));
+    int32_t *cs, *cid, *seg, *cpar, *cminid, *clab, *csz, *kstart, *kids, *pnodes, *poff, *ssel, *Kp, *rc, *rl, *mlist,
+        *llist, *mk, *rk;
+    uint64_t *key1, *key2, *jw, *tw, *lw;
+    double *val1, *val2, *stab, *cpv, *rs, *mpre, *postv;
+    int *jflags;
+    unsigned long long *groot;
+    char *fz;
     const size_t fz_bytes = fz_layout(m);
+    carve(ctx, A_FLAT1, [&](Carver &cv) {
+        cs = cv.take<int32_t>(m), cid = cv.take<int32_t>(m);
+        key1 = cv.take<uint64_t>(m), key2 = cv.take<uint64_t>(m);
+        val1 = cv.take<double>(m), val2 = cv.take<double>(m);
+        seg = cv.take<int32_t>(m);
+        stab = cv.take<double>(m);
+        cpar = cv.take<int32_t>(m), cminid = cv.take<int32_t>(m), clab = cv.take<int32_t>(m);
+        jflags = cv.take<int32_t>(64);
+        groot = cv.take<unsigned long long>(1);  // outlier scores: the root's eps_max
+        csz = cv.take<int32_t>(m), kstart = cv.take<int32_t>(m), kids = cv.take<int32_t>(m);
+        pnodes = cv.take<int32_t>(m), poff = cv.take<int32_t>(m);
+        ssel = cv.take<int32_t>(m), Kp = cv.take<int32_t>(m), rc = cv.take<int32_t>(m);
+        rl = cv.take<int32_t>(m), mlist = cv.take<int32_t>(m), llist = cv.take<int32_t>(m);
+        jw = cv.take<uint64_t>(m), tw = cv.take<uint64_t>(m);
+        cpv = cv.take<double>(m);
+        lw = cv.take<uint64_t>(m);
+        rs = cv.take<double>(m), mpre = cv.take<double>(m), postv = cv.take<double>(m);
+        fz = cv.take<char>(fz_bytes);  // the zeroed block
+        mk = cv.take<int32_t>(n), rk = cv.take<int32_t>(n);
+    });
     int32_t *nch = (int32_t *)fz, *kcur = nch + m, *plen = kcur + m, *maxld = plen + m;  // (m ints)
     int32_t *mcount = maxld + 1, *lcount = maxld + 2, *pwide = maxld + m;
     unsigned long long *hkey = (unsigned long long *)(pwide + 2 * m);
     int *ffl = (int *)(hkey + m);  // 192 jump flags
-    int32_t *mk = cv2.take<int32_t>(n), *rk = cv2.take<int32_t>(n);
     // guaranteed reach 5x per fl_jump launch (see fl_jump_check): ceil(log5 m) launches + one
     int rounds = 2;
     for (int64_t span = 5; span < m; span *= 5) rounds++;
@@ -2308,12 +2267,7 @@ static void flat_device_impl(hdb_ctx *ctx, const int32_t *va, const int32_t *vb,
     hipLaunchKernelGGL(fl_nodes, dim3(g), dim3(256), 0, st, na);
     hipLaunchKernelGGL(fl_starts, dim3(g), dim3(256), 0, st, top, pnode, dc.esize, nvalid, m, mcs, is_start, cs);
     jump_all(cs, rounds);
-    {
-        size_t tb = 0;
-        HIP_CHECK(rocprim::exclusive_scan(nullptr, tb, is_start, cid, 0, (size_t)m, rocprim::plus<int32_t>(), st));
-        void *tmp = arena(ctx, A_FLAT_TMP, tb);
-        HIP_CHECK(rocprim::exclusive_scan(tmp, tb, is_start, cid, 0, (size_t)m, rocprim::plus<int32_t>(), st));
-    }
+    exclusive_sum(ctx, A_FLAT_TMP, is_start, cid, m);
     // ---- 4. stabilities: chains grouped by cluster, descending level inside.  The cluster
     // count K stays on the device (no host round trip): kernels read it, and the key width
     // is bounded by m (the same number of radix passes at every K of this size)
@@ -2325,11 +2279,8 @@ static void flat_device_impl(hdb_ctx *ctx, const int32_t *va, const int32_t *vb,
     if (ctx->ssort && tpl.nb) {  // the terms' keys are unique (rank in the low word); non-terms last
         ssort(tpl, (char *)arena(ctx, A_SS, tpl.bytes), TermKeyF{key1}, TermEmitF{val1, key2, val2}, st);
     } else {
-        size_t tb = 0;
         // keys of non-terms are all-ones: sorting on the cluster bits + 32 keeps them last
-        HIP_CHECK(sort_pairs(nullptr, tb, key1, key2, val1, val2, m, 0, 64, st));
-        void *tmp = arena(ctx, A_FLAT_TMP, tb);
-        HIP_CHECK(sort_pairs(tmp, tb, key1, key2, val1, val2, m, 0, std::min(64, 32 + kb + 1), st));
+        sort_pairs(ctx, A_FLAT_TMP, key1, key2, val1, val2, m, 0, std::min(64, 32 + kb + 1));
     }
     int32_t *seg_hi = (int32_t *)key1;  // key1 is free after the sort
     hipLaunchKernelGGL(fill_i32, dim3(g), dim3(256), 0, st, seg, m, -1);
@@ -2352,23 +2303,13 @@ static void flat_device_impl(hdb_ctx *ctx, const int32_t *va, const int32_t *vb,
     // zero: nch, kcur, plen, maxld, hkey (contiguous) and the jump flags
     HIP_CHECK(hipMemsetAsync(fz, 0, fz_bytes, st));
     hipLaunchKernelGGL(fo_children, dim3(g), dim3(256), 0, st, cpar, csz, Kp, nch, hkey, err);
-    {
-        size_t tb = 0;
-        HIP_CHECK(rocprim::exclusive_scan(nullptr, tb, nch, kstart, 0, (size_t)m, rocprim::plus<int32_t>(), st));
-        void *tmp = arena(ctx, A_FLAT_TMP, tb);
-        HIP_CHECK(rocprim::exclusive_scan(tmp, tb, nch, kstart, 0, (size_t)m, rocprim::plus<int32_t>(), st));
-    }
+    exclusive_sum(ctx, A_FLAT_TMP, nch, kstart, m);
     hipLaunchKernelGGL(fo_kids_fill, dim3(g), dim3(256), 0, st, cpar, Kp, kstart, kcur, kids, err);
     hipLaunchKernelGGL(fo_paths_init, dim3(g), dim3(256), 0, st, cpar, cminid, Kp, nch, hkey, kstart, kids, jw, err);
     jump64(fo_jump_sum, jw, ffl);
     hipLaunchKernelGGL(fo_paths_meta, dim3(g), dim3(256), 0, st, cpar, Kp, nch, jw, plen, lw, err);
     jump64(fo_jump_sum, lw, ffl + 128);
-    {
-        size_t tb = 0;
-        HIP_CHECK(rocprim::exclusive_scan(nullptr, tb, plen, poff, 0, (size_t)m, rocprim::plus<int32_t>(), st));
-        void *tmp = arena(ctx, A_FLAT_TMP, tb);
-        HIP_CHECK(rocprim::exclusive_scan(tmp, tb, plen, poff, 0, (size_t)m, rocprim::plus<int32_t>(), st));
-    }
+    exclusive_sum(ctx, A_FLAT_TMP, plen, poff, m);
     hipLaunchKernelGGL(fo_paths_nodes, dim3(g), dim3(256), 0, st, Kp, jw, poff, lw, pnodes, maxld, err);
     hipLaunchKernelGGL(fo_paths_rec, dim3(g), dim3(256), 0, st, Kp, pnodes, nch, hkey, kstart, kids, stab, rc, rl, rs,
                        mlist, mcount, jw, pwide, err);
@@ -2387,12 +2328,7 @@ static void flat_device_impl(hdb_ctx *ctx, const int32_t *va, const int32_t *vb,
     jump64(fo_sel_jump, tw, ffl + 64);
     HIP_CHECK(hipMemsetAsync(mk, 0, sizeof(int32_t) * n, st));
     hipLaunchKernelGGL(fo_mark, dim3(g), dim3(256), 0, st, tw, cminid, Kp, mk, err);
-    {
-        size_t tb = 0;
-        HIP_CHECK(rocprim::exclusive_scan(nullptr, tb, mk, rk, 0, (size_t)n, rocprim::plus<int32_t>(), st));
-        void *tmp = arena(ctx, A_FLAT_TMP, tb);
-        HIP_CHECK(rocprim::exclusive_scan(tmp, tb, mk, rk, 0, (size_t)n, rocprim::plus<int32_t>(), st));
-    }
+    exclusive_sum(ctx, A_FLAT_TMP, mk, rk, n);
     hipLaunchKernelGGL(fo_labels, dim3(g), dim3(256), 0, st, tw, cminid, rk, Kp, clab, err);
     hipLaunchKernelGGL(fo_count, dim3(1), dim3(64), 0, st, mk, rk, n, (int64_t *)(words + 3), err);
     if (!scores && !tree) {
@@ -2419,10 +2355,7 @@ static void flat_device_impl(hdb_ctx *ctx, const int32_t *va, const int32_t *vb,
             HIP_CHECK(hipMemcpyAsync(pin, words, sizeof(int64_t) * 4, hipMemcpyDeviceToHost, st));
             HIP_CHECK(hipMemcpyAsync(pin + 4, Kp, sizeof(int32_t), hipMemcpyDeviceToHost, st));
             HIP_CHECK(hipStreamSynchronize(st));
-            const int et = (int)pin[1];
-            if (et & FE_CYCLE) HDB_THROW(HDB_EINVAL, "flat labels: the edges contain a cycle");
-            if (et & FE_ROOTS) HDB_THROW(HDB_EINVAL, "flat labels: the edges are not a spanning tree");
-            if (et & FE_JUMP) HDB_THROW(HDB_EDEVICE, "flat labels: pointer jumping did not converge in its launch budget");
+            throw_tree_errors((int)pin[1]);
             const int32_t K = *(int32_t *)(pin + 4);
             if (K < 1 || K > m) HDB_THROW(HDB_EDEVICE, "cluster tree: cluster count out of range");
             *tree->n_tree = K;
@@ -2438,13 +2371,10 @@ static void flat_device_impl(hdb_ctx *ctx, const int32_t *va, const int32_t *vb,
             const int32_t *perm = ids1;
             if (K > 2) {  // stable LSD: by smallest member first, then by birth level (descending)
                 const int64_t ks = K - 1;
-                size_t tb = 0, tb2 = 0;
-                HIP_CHECK(sort_pairs(nullptr, tb, kmin1, kmin2, ids1, ids2, ks, 0, 32, st));
-                HIP_CHECK(sort_pairs(nullptr, tb2, kb2, kb1, ids2, ids1, ks, 0, 64, st));
-                void *tmp = arena(ctx, A_FLAT_TMP, std::max(tb, tb2));
-                HIP_CHECK(sort_pairs(tmp, tb, kmin1, kmin2, ids1, ids2, ks, 0, 32, st));
+                // (both take A_FLAT_TMP in turn; the arena only grows, so from the second call on neither moves it)
+                sort_pairs(ctx, A_FLAT_TMP, kmin1, kmin2, ids1, ids2, ks, 0, 32);
                 hipLaunchKernelGGL(ct_birth_keys, dim3(gk), dim3(256), 0, st, kb1, ids2, (int32_t)ks, kb2);
-                HIP_CHECK(sort_pairs(tmp, tb2, kb2, kb1, ids2, ids1, ks, 0, 64, st));
+                sort_pairs(ctx, A_FLAT_TMP, kb2, kb1, ids2, ids1, ks, 0, 64);
             }
             hipLaunchKernelGGL(ct_inverse, dim3(gk), dim3(256), 0, st, perm, K, inv);
             TreeArr ta{perm, inv, cstart, cpar, cminid, pnode, dc.esize, rk, ew, stab, dw, tw, *tree, K};
@@ -2476,10 +2406,7 @@ static void flat_device_impl(hdb_ctx *ctx, const int32_t *va, const int32_t *vb,
     HIP_CHECK(hipMemcpyAsync(pin, words, sizeof(int64_t) * 4, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipMemcpyAsync(pin + 4, Kp, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
-    const int e1 = (int)pin[1];
-    if (e1 & FE_CYCLE) HDB_THROW(HDB_EINVAL, "flat labels: the edges contain a cycle");
-    if (e1 & FE_ROOTS) HDB_THROW(HDB_EINVAL, "flat labels: the edges are not a spanning tree");
-    if (e1 & FE_JUMP) HDB_THROW(HDB_EDEVICE, "flat labels: pointer jumping did not converge in its launch budget");
+    throw_tree_errors((int)pin[1]);
     if (n_clusters) *n_clusters = pin[3];
     ctx->stats["flat_clusters_total"] = *(int32_t *)(pin + 4);  // condensed-tree clusters incl. the root
 }
@@ -2512,21 +2439,17 @@ void labels_at_levels_device(hdb_ctx *ctx, const int32_t *parent, const double *
     int J = 1;
     while ((int64_t(1) << J) < K) J++;  // 2^J >= K > the deepest chain
     const int64_t stride = K + 1;
-    Carver probe;
-    auto layout = [&](Carver &cv) {
-        cv.take<int64_t>(1);                  // error word
-        cv.take<double>(stride);              // births by label
-        cv.take<int32_t>(stride * J);         // ancestor rows
-        for (int k = 0; k < 2; k++) cv.take<unsigned long long>(L);  // level keys, sorted
-        for (int k = 0; k < 2; k++) cv.take<int32_t>(L);             // their rows
-    };
-    layout(probe);
-    Carver cv{(char *)arena(ctx, A_FLAT1, probe.off), 0};
-    int *err = (int *)cv.take<int64_t>(1);
-    double *bt = cv.take<double>(stride);
-    int32_t *anc = cv.take<int32_t>(stride * J);
-    unsigned long long *key1 = cv.take<unsigned long long>(L), *key2 = cv.take<unsigned long long>(L);
-    int32_t *row1 = cv.take<int32_t>(L), *row2 = cv.take<int32_t>(L);
+    int *err;
+    double *bt;
+    int32_t *anc, *row1, *row2;
+    unsigned long long *key1, *key2;
+    carve(ctx, A_FLAT1, [&](Carver &cv) {
+        err = (int *)cv.take<int64_t>(1);  // error word
+        bt = cv.take<double>(stride);      // births by label
+        anc = cv.take<int32_t>(stride * J);  // ancestor rows
+        key1 = cv.take<unsigned long long>(L), key2 = cv.take<unsigned long long>(L);  // level keys, sorted
+        row1 = cv.take<int32_t>(L), row2 = cv.take<int32_t>(L);                        // their rows
+    });
     HIP_CHECK(hipMemsetAsync(err, 0, sizeof(int64_t), st));
     const int gk = grid_for(stride);
     hipLaunchKernelGGL(lc_init, dim3(gk), dim3(256), 0, st, parent, birth, (int32_t)K, anc, bt, err);
@@ -2537,10 +2460,7 @@ void labels_at_levels_device(hdb_ctx *ctx, const int32_t *parent, const double *
         const unsigned long long *skey = key1;
         const int32_t *srow = row1;
         if (L > 1) {
-            size_t tb = 0;
-            HIP_CHECK(sort_pairs(nullptr, tb, key1, key2, row1, row2, L, 0, 64, st));
-            void *tmp = arena(ctx, A_FLAT_TMP, tb);
-            HIP_CHECK(sort_pairs(tmp, tb, key1, key2, row1, row2, L, 0, 64, st));
+            sort_pairs(ctx, A_FLAT_TMP, key1, key2, row1, row2, L, 0, 64);
             skey = key2, srow = row2;
         }
         if (n > 0)
@@ -2570,21 +2490,17 @@ void predict_labels_device(hdb_ctx *ctx, const int32_t *parent, const double *bi
     int J = 1;
     while ((int64_t(1) << J) < K) J++;  // 2^J >= K > the deepest chain
     const int64_t stride = K + 1;
-    Carver probe;
-    auto layout = [&](Carver &cv) {
-        cv.take<int64_t>(1);                     // error word
-        cv.take<double>(stride);                 // births by label
-        cv.take<int32_t>(stride * J);            // ancestor rows
-        cv.take<unsigned long long>(stride);     // eps_max keys
-        for (int k = 0; k < 2; k++) cv.take<int32_t>(stride);  // nearest selected flat label, two buffers
-    };
-    layout(probe);
-    Carver cv{(char *)arena(ctx, A_FLAT1, probe.off), 0};
-    int *err = (int *)cv.take<int64_t>(1);
-    double *bt = cv.take<double>(stride);
-    int32_t *anc = cv.take<int32_t>(stride * J);
-    unsigned long long *em = cv.take<unsigned long long>(stride);
-    int32_t *near_a = cv.take<int32_t>(stride), *near_b = cv.take<int32_t>(stride);
+    int *err;
+    double *bt;
+    int32_t *anc, *near_a, *near_b;
+    unsigned long long *em;
+    carve(ctx, A_FLAT1, [&](Carver &cv) {
+        err = (int *)cv.take<int64_t>(1);            // error word
+        bt = cv.take<double>(stride);                // births by label
+        anc = cv.take<int32_t>(stride * J);          // ancestor rows
+        em = cv.take<unsigned long long>(stride);    // eps_max keys
+        near_a = cv.take<int32_t>(stride), near_b = cv.take<int32_t>(stride);  // nearest selected flat label, two buffers
+    });
     HIP_CHECK(hipMemsetAsync(err, 0, sizeof(int64_t), st));
     const int gk = grid_for(stride);
     hipLaunchKernelGGL(lc_init, dim3(gk), dim3(256), 0, st, parent, birth, (int32_t)K, anc, bt, err);

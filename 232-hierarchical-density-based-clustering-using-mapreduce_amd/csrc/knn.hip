@@ -218,13 +218,15 @@ void knn_lists_device(hdb_ctx *ctx, const double *X_dev, int64_t n, int d, int k
     if (metric == HDB_METRIC_EUCLIDEAN) {
         int dp = (d + 1) & ~1;
         int df = d <= 4 ? 4 : (d <= 8 ? 8 : 16);
-        // carve: Xp (FP64 padded) | Xf (FP32 shifted) | bbox lo/hi | params
-        size_t b_xp = ((sizeof(double) * (size_t)(n * dp)) + 255) & ~size_t(255);
-        size_t b_xf = ((sizeof(float) * (size_t)(n * df)) + 255) & ~size_t(255);
-        char *base = (char *)arena(ctx, A_PAD, b_xp + b_xf + 1024 + 64 * 16);
-        double *Xp = (double *)base;
-        float *Xf = (float *)(base + b_xp);
-        double *blo = (double *)(base + b_xp + b_xf), *bhi = blo + 64, *prm = bhi + 64;
+        // Xp (FP64 padded) | Xf (FP32 shifted) | bbox lo, hi and the params, 64 doubles apart in one array
+        double *Xp, *blo;
+        float *Xf;
+        carve(ctx, A_PAD, [&](Carver &cv) {
+            Xp = cv.take<double>(n * dp);
+            Xf = cv.take<float>(n * df);
+            blo = cv.take<double>(256);
+        });
+        double *bhi = blo + 64, *prm = bhi + 64;
         pack_rows(ctx, X_dev, n, d, dp, Xp);
         g_screen = F32Screen();
         if (d <= 16 && !ctx->force_fp64) {

@@ -1636,28 +1636,23 @@ static bool knn_mfma_dp(hdb_ctx *ctx, const double *X, int64_t n, int d, int KC,
     // row capacity: the pruned layout pads every k-means cluster to a multiple of 256 rows
     const int64_t n_cap = prune ? ceil_div(n + 256 * (int64_t)km_k(n), (int64_t)512) * 512 : n_pad;
     const int nb = (int)std::min<int64_t>(1024, std::max<int64_t>(1, n / 64));
-    auto rnd = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t bytes = 2 * rnd(sizeof(__bf16) * (size_t)(n_cap * DP)) + 3 * rnd(8 * (size_t)n_cap) +
-                         2 * rnd(8 * (size_t)nb * d) + rnd(8 * (size_t)d) + 256 + 256 +
-                         rnd(4 * (size_t)(n_cap / 32) * S_CST) + 2 * rnd(4 * (size_t)n_cap);
-    char *base = (char *)arena(ctx, A_WORK3, bytes);
-    size_t off = 0;
-    auto take = [&](size_t b) {
-        char *p = base + off;
-        off += rnd(b);
-        return p;
-    };
-    __bf16 *Xh = (__bf16 *)take(sizeof(__bf16) * (size_t)(n_cap * DP));
-    __bf16 *Xl = (__bf16 *)take(sizeof(__bf16) * (size_t)(n_cap * DP));
-    double *nrm2 = (double *)take(8 * (size_t)n_cap), *nrm = (double *)take(8 * (size_t)n_cap);
-    double *psum = (double *)take(8 * (size_t)nb * d), *pmax = (double *)take(8 * (size_t)nb * d);
-    double *mu = (double *)take(8 * (size_t)d);
-    double *thr = (double *)take(8 * (size_t)n_cap);
-    double *prm = (double *)take(256);
-    unsigned long long *stats = (unsigned long long *)take(256);
-    float *cst = (float *)take(4 * (size_t)(n_cap / 32) * S_CST);
-    int *log_cnt = (int *)take(8 * (size_t)n_cap);  // per query, or per half-query (register top lists, KC <= 15)
-    float *thr_f = (float *)take(4 * (size_t)n_cap);
+    __bf16 *Xh, *Xl;
+    double *nrm2, *nrm, *psum, *pmax, *mu, *thr, *prm;
+    unsigned long long *stats;
+    float *cst, *thr_f;
+    int *log_cnt;
+    carve(ctx, A_WORK3, [&](Carver &cv) {
+        Xh = cv.take<__bf16>(n_cap * DP), Xl = cv.take<__bf16>(n_cap * DP);
+        nrm2 = cv.take<double>(n_cap), nrm = cv.take<double>(n_cap);
+        psum = cv.take<double>((int64_t)nb * d), pmax = cv.take<double>((int64_t)nb * d);
+        mu = cv.take<double>(d);
+        thr = cv.take<double>(n_cap);
+        prm = cv.take<double>(32);
+        stats = cv.take<unsigned long long>(32);
+        cst = cv.take<float>(n_cap / 32 * S_CST);
+        log_cnt = cv.take<int>(2 * n_cap);  // per query, or per half-query (register top lists, KC <= 15)
+        thr_f = cv.take<float>(n_cap);
+    });
     hipStream_t st = ctx->stream;
     hipLaunchKernelGGL(col_stats_kernel, dim3(nb), dim3(256), 0, st, X, n, d, nb, psum, pmax);
     hipLaunchKernelGGL(centre_kernel, dim3(1), dim3(256), 0, st, psum, pmax, nb, n, d, mu, prm);
@@ -1673,42 +1668,23 @@ static bool knn_mfma_dp(hdb_ctx *ctx, const double *X, int64_t n, int d, int KC,
     if (single) {
         using Cf = ScreenCfg<DP>;
         // layout (A_ORDER): perm, k-means scratch, query-group and superblock balls
-        const int64_t n_sortcap = std::max<int64_t>(n, 1);
-        size_t sort_tb = 0;
-        HIP_CHECK(sort_pairs(nullptr, sort_tb, (const unsigned long long *)nullptr, (unsigned long long *)nullptr,
-                             (const int *)nullptr, (int *)nullptr, n_sortcap, 0, 64, st));
-        const size_t obytes = rnd(4 * (size_t)n_cap) + 3 * rnd(4 * (size_t)n) + 2 * rnd(8 * (size_t)n) +
-                              rnd(sort_tb) + rnd(4 * (size_t)n * KM_P) + 2 * rnd(4 * KM_K * KM_P) +
-                              rnd(4 * KM_K) + 3 * rnd(4 * KM_K) + rnd(8 * (size_t)(n_cap / 128) * DP) +
-                              rnd(16 * (size_t)(n_cap / 128)) + rnd(8 * (size_t)NSB_MAX * DP) + rnd(16 * NSB_MAX) +
-                              2 * rnd(4 * NSB_MAX);
-        char *ob = (char *)arena(ctx, A_ORDER, obytes);
-        size_t oo = 0;
-        auto otake = [&](size_t b) {
-            char *p = ob + oo;
-            oo += rnd(b);
-            return p;
-        };
-        int *perm = (int *)otake(4 * (size_t)n_cap);
+        int *perm, *sb_blk_d, *sb_nblk_d;
+        double *qctr, *qrn, *sctr, *srn;
         KmBufs kb;
-        kb.vals = (int *)otake(4 * (size_t)n);
-        kb.rows = (int *)otake(4 * (size_t)n);
-        kb.asg = (int *)otake(4 * (size_t)n);
-        kb.k1 = (unsigned long long *)otake(8 * (size_t)n);
-        kb.k2 = (unsigned long long *)otake(8 * (size_t)n);
-        kb.tmp = otake(sort_tb);
-        kb.tmp_bytes = sort_tb;
-        kb.Y = (float *)otake(4 * (size_t)n * KM_P);
-        kb.C = (float *)otake(4 * KM_K * KM_P);
-        kb.sum = (float *)otake(4 * KM_K * KM_P);
-        kb.cnt = (float *)otake(4 * KM_K);
-        kb.hist = (int *)otake(4 * KM_K);
-        kb.start = (int *)otake(4 * KM_K);
-        kb.off = (int *)otake(4 * KM_K);
-        double *qctr = (double *)otake(8 * (size_t)(n_cap / 128) * DP);
-        double *qrn = (double *)otake(16 * (size_t)(n_cap / 128));
-        double *sctr = (double *)otake(8 * (size_t)NSB_MAX * DP), *srn = (double *)otake(16 * NSB_MAX);
-        int *sb_blk_d = (int *)otake(4 * NSB_MAX), *sb_nblk_d = (int *)otake(4 * NSB_MAX);
+        kb.tmp_bytes = sort_pairs_bytes<unsigned long long, int>(n, 0, 64);
+        carve(ctx, A_ORDER, [&](Carver &cv) {
+            perm = cv.take<int>(n_cap);
+            kb.vals = cv.take<int>(n), kb.rows = cv.take<int>(n), kb.asg = cv.take<int>(n);
+            kb.k1 = cv.take<unsigned long long>(n), kb.k2 = cv.take<unsigned long long>(n);
+            kb.tmp = cv.take<char>(kb.tmp_bytes);
+            kb.Y = cv.take<float>(n * KM_P);
+            kb.C = cv.take<float>(KM_K * KM_P), kb.sum = cv.take<float>(KM_K * KM_P);
+            kb.cnt = cv.take<float>(KM_K);
+            kb.hist = cv.take<int>(KM_K), kb.start = cv.take<int>(KM_K), kb.off = cv.take<int>(KM_K);
+            qctr = cv.take<double>(n_cap / 128 * DP), qrn = cv.take<double>(2 * (n_cap / 128));
+            sctr = cv.take<double>(NSB_MAX * DP), srn = cv.take<double>(2 * NSB_MAX);
+            sb_blk_d = cv.take<int>(NSB_MAX), sb_nblk_d = cv.take<int>(NSB_MAX);
+        });
         std::vector<int> sb_blk, sb_nblk;
         int64_t n_lay = n;
         if (prune) {

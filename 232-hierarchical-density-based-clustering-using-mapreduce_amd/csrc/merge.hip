@@ -68,10 +68,12 @@ void sort_edges_desc_device(hdb_ctx *ctx, int32_t *va, int32_t *vb, double *w, i
         const SsPlan pl = ss_plan(ne, ctx->ssort_cap);
         if (pl.nb) {
             KernelTimer t(ctx, "merge_sort");
-            const size_t eb = ((size_t)ne * 4 + 255) & ~size_t(255);
-            char *tmp = (char *)arena(ctx, A_WORK3, 2 * eb + (size_t)ne * 8);
-            int32_t *ta = (int32_t *)tmp, *tb_ = (int32_t *)(tmp + eb);
-            double *tw = (double *)(tmp + 2 * eb);
+            int32_t *ta, *tb_;
+            double *tw;
+            carve(ctx, A_WORK3, [&](Carver &cv) {
+                ta = cv.take<int32_t>(ne), tb_ = cv.take<int32_t>(ne);
+                tw = cv.take<double>(ne);
+            });
             ssort(pl, (char *)arena(ctx, A_SS, pl.bytes), DescKeyF{w}, GatherEmitF{va, vb, w, ta, tb_, tw}, ctx->stream);
             HIP_CHECK(hipMemcpyAsync(va, ta, sizeof(int32_t) * ne, hipMemcpyDeviceToDevice, ctx->stream));
             HIP_CHECK(hipMemcpyAsync(vb, tb_, sizeof(int32_t) * ne, hipMemcpyDeviceToDevice, ctx->stream));
@@ -79,20 +81,14 @@ void sort_edges_desc_device(hdb_ctx *ctx, int32_t *va, int32_t *vb, double *w, i
             return;
         }
     }
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        size_t o = off;
-        off += (bytes + 255) & ~size_t(255);
-        return o;
-    };
-    size_t o_k = carve(sizeof(double) * ne), o_k2 = carve(sizeof(double) * ne), o_i = carve(sizeof(int32_t) * ne),
-           o_p = carve(sizeof(int32_t) * ne), o_a = carve(sizeof(int32_t) * ne), o_b = carve(sizeof(int32_t) * ne),
-           o_w = carve(sizeof(double) * ne);
-    char *base = (char *)arena(ctx, A_WORK3, off);
-    double *keys = (double *)(base + o_k), *keys2 = (double *)(base + o_k2);
-    int32_t *iota = (int32_t *)(base + o_i), *perm = (int32_t *)(base + o_p);
-    int32_t *ta = (int32_t *)(base + o_a), *tb_ = (int32_t *)(base + o_b);
-    double *tw = (double *)(base + o_w);
+    double *keys, *keys2, *tw;
+    int32_t *iota, *perm, *ta, *tb_;
+    carve(ctx, A_WORK3, [&](Carver &cv) {
+        keys = cv.take<double>(ne), keys2 = cv.take<double>(ne);
+        iota = cv.take<int32_t>(ne), perm = cv.take<int32_t>(ne);
+        ta = cv.take<int32_t>(ne), tb_ = cv.take<int32_t>(ne);
+        tw = cv.take<double>(ne);
+    });
     int g = (int)std::min<int64_t>(ceil_div(ne, 256), 8192);
     hipStream_t st = ctx->stream;
     KernelTimer t(ctx, "merge_sort");
@@ -100,10 +96,7 @@ void sort_edges_desc_device(hdb_ctx *ctx, int32_t *va, int32_t *vb, double *w, i
     // prefix, place both parts by binary search: 0.60 ms against 0.41, a sync plus 2M binary
     // searches; not kept)
     hipLaunchKernelGGL(edge_keys_kernel, dim3(g), dim3(256), 0, st, w, ne, keys, iota);
-    size_t tb = 0;
-    HIP_CHECK(sort_pairs_desc(nullptr, tb, keys, keys2, iota, perm, ne, 0, 64, st));
-    void *tmp = arena(ctx, A_SORT, tb);
-    HIP_CHECK(sort_pairs_desc(tmp, tb, keys, keys2, iota, perm, ne, 0, 64, st));
+    sort_pairs_desc(ctx, A_SORT, keys, keys2, iota, perm, ne, 0, 64);
     hipLaunchKernelGGL(edge_gather_kernel, dim3(g), dim3(256), 0, st, perm, ne, va, vb, w, ta, tb_, tw);
     HIP_CHECK(hipMemcpyAsync(va, ta, sizeof(int32_t) * ne, hipMemcpyDeviceToDevice, st));
     HIP_CHECK(hipMemcpyAsync(vb, tb_, sizeof(int32_t) * ne, hipMemcpyDeviceToDevice, st));
@@ -196,12 +189,16 @@ void merge_sorted_runs_device(hdb_ctx *ctx, const int32_t *va, const int32_t *vb
     const int64_t ne = off.back();
     if (ne <= 0) return;
     KernelTimer t(ctx, "merge_sorted_runs");
-    // scratch: the ping-pong buffer, the run-end flags, the error word
-    const size_t sb = ((size_t)ne * 16 + 255) & ~size_t(255);
-    char *base = (char *)arena(ctx, A_WORK3, sb + (size_t)ne * 8 + 512);
-    int32_t *ta = (int32_t *)base, *tb_ = ta + ne;
-    double *tw = (double *)(base + (((size_t)ne * 8 + 255) & ~size_t(255)));
-    int64_t *flag = (int64_t *)(base + sb);
+    // scratch: the ping-pong buffer, then the run-end flags with the error word in the 512 bytes
+    // behind them (one memset clears both)
+    int32_t *ta, *tb_;
+    double *tw;
+    int64_t *flag;
+    carve(ctx, A_WORK3, [&](Carver &cv) {
+        ta = cv.take<int32_t>(2 * ne), tb_ = ta + ne;
+        tw = cv.take<double>(ne);
+        flag = cv.take<int64_t>(ne + 64);
+    });
     int *err = (int *)(flag + ne);
     HIP_CHECK(hipMemsetAsync(flag, 0, (size_t)ne * 8 + 512, st));
     std::vector<int64_t> ends;
@@ -301,29 +298,20 @@ void local_mst_ids_device(hdb_ctx *ctx, const int32_t *ids, int64_t n, const int
     const int g = (int)std::min<int64_t>(ceil_div(ne, 256), 8192);
     int32_t *keys = nullptr, *pos = nullptr;
     int *err = nullptr;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        size_t o = off;
-        off += (bytes + 255) & ~size_t(255);
-        return o;
-    };
-    const size_t o_e = carve(sizeof(int) * 4), o_k = carve(sizeof(int32_t) * std::max<int64_t>(n, 1)),
-                 o_k2 = carve(sizeof(int32_t) * std::max<int64_t>(n, 1)), o_p = carve(sizeof(int32_t) * std::max<int64_t>(n, 1)),
-                 o_p2 = carve(sizeof(int32_t) * std::max<int64_t>(n, 1));
-    char *base = (char *)arena(ctx, A_WORK3, off);
-    err = (int *)(base + o_e);
+    int32_t *k1, *p1, *keys2, *pos2;
+    carve(ctx, A_WORK3, [&](Carver &cv) {
+        err = cv.take<int>(4);
+        k1 = cv.take<int32_t>(n), keys2 = cv.take<int32_t>(n);
+        p1 = cv.take<int32_t>(n), pos2 = cv.take<int32_t>(n);
+    });
     HIP_CHECK(hipMemsetAsync(err, 0, sizeof(int) * 4, st));
     if (ids) {
         if (n > INT32_MAX) HDB_THROW(HDB_EINVAL, "too many vertices");
-        int32_t *k1 = (int32_t *)(base + o_k), *p1 = (int32_t *)(base + o_p);
-        keys = (int32_t *)(base + o_k2);
-        pos = (int32_t *)(base + o_p2);
+        keys = keys2;
+        pos = pos2;
         HIP_CHECK(hipMemcpyAsync(k1, ids, sizeof(int32_t) * n, hipMemcpyDefault, st));
         hipLaunchKernelGGL(pos_fill_kernel, dim3((int)std::min<int64_t>(ceil_div(n, 256), 8192)), dim3(256), 0, st, p1, n);
-        size_t tb = 0;
-        HIP_CHECK(sort_pairs(nullptr, tb, k1, keys, p1, pos, n, 0, 32, st));
-        void *tmp = arena(ctx, A_SORT, tb);
-        HIP_CHECK(sort_pairs(tmp, tb, k1, keys, p1, pos, n, 0, 32, st));
+        sort_pairs(ctx, A_SORT, k1, keys, p1, pos, n, 0, 32);
         hipLaunchKernelGGL(local_ids_dup_kernel, dim3((int)std::min<int64_t>(ceil_div(n, 256), 8192)), dim3(256), 0, st,
                            keys, n, err);
     }

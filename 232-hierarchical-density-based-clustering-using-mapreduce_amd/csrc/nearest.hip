@@ -223,12 +223,9 @@ static void stable_sort_by_key(hdb_ctx *ctx, const int32_t *keys, int64_t n, int
                                int32_t *perm_tmp) {
     int g = (int)std::min<int64_t>(ceil_div(n, 256), 4096);
     hipLaunchKernelGGL(iota_kernel, dim3(g), dim3(256), 0, ctx->stream, perm_tmp, n);
-    size_t tb = 0;
-    HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys, keys_out, perm_tmp, perm_out, (int)n, 0, 32,
-                                                 ctx->stream));
-    void *tmp = arena(ctx, A_SORT, tb);
-    HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, keys, keys_out, perm_tmp, perm_out, (int)n, 0, 32,
-                                                 ctx->stream));
+    with_tmp(ctx, A_SORT, [&](void *tmp, size_t &tb) {
+        return hipcub::DeviceRadixSort::SortPairs(tmp, tb, keys, keys_out, perm_tmp, perm_out, (int)n, 0, 32, ctx->stream);
+    });
 }
 
 // ------------------------------------------------------------------ K3g: grouped samples
@@ -478,16 +475,6 @@ static bool nearest_grouped(hdb_ctx *ctx, const double *X, int64_t n, const doub
             }
         }
     }
-    // device scratch (A_WORK1): groups, ids, boxes, tree, key tables, keys/order + sort
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        size_t o = off;
-        off += (bytes + 255) & ~size_t(255);
-        return o;
-    };
-    size_t tb = 0;
-    HIP_CHECK(sort_pairs(nullptr, tb, (const uint32_t *)nullptr, (uint32_t *)nullptr, (const int32_t *)nullptr,
-                         (int32_t *)nullptr, n, 0, 32, st));
     // runs of SB groups behind one union box
     constexpr int SB = NNG_SB;
     const int ns = (ng + SB - 1) / SB;
@@ -502,18 +489,25 @@ static bool nearest_grouped(hdb_ctx *ctx, const double *X, int64_t n, const doub
             hsb[(size_t)s2 * 2 * d + c] = lo;
             hsb[(size_t)s2 * 2 * d + d + c] = hi;
         }
-    const size_t o_sb = carve(8 * hsb.size());
-    const size_t o_g = carve(sizeof(double) * hg.size()), o_i = carve(4 * hi_.size()), o_b = carve(8 * hb.size()),
-                 o_t = carve(sizeof(KdNode) * tree.size()), o_kt = carve(16 * (size_t)nk), o_k1 = carve(4 * (size_t)n),
-                 o_k2 = carve(4 * (size_t)n), o_v1 = carve(4 * (size_t)n), o_v2 = carve(4 * (size_t)n),
-                 o_ks = carve(4 * (size_t)n), o_tmp = carve(tb);
-    char *base = (char *)arena(ctx, A_WORK1, off);
-    double *dg = (double *)(base + o_g), *db = (double *)(base + o_b);
-    int32_t *di = (int32_t *)(base + o_i);
-    KdNode *dt = (KdNode *)(base + o_t);
-    int32_t *dkeys = (int32_t *)(base + o_kt), *droot = dkeys + nk, *dglo = droot + nk, *dghi = dglo + nk;
-    uint32_t *k1 = (uint32_t *)(base + o_k1), *k2 = (uint32_t *)(base + o_k2);
-    int32_t *v1 = (int32_t *)(base + o_v1), *v2 = (int32_t *)(base + o_v2), *kslot = (int32_t *)(base + o_ks);
+    // device scratch (A_WORK1): boxes, groups, ids, tree, the four key tables in one array, keys/order + sort
+    size_t tb = sort_pairs_bytes<uint32_t, int32_t>(n, 0, 32);
+    double *dsb, *dg, *db;
+    int32_t *di, *dkeys, *v1, *v2, *kslot;
+    KdNode *dt;
+    uint32_t *k1, *k2;
+    char *sort_tmp;
+    carve(ctx, A_WORK1, [&](Carver &cv) {
+        dsb = cv.take<double>(hsb.size());
+        dg = cv.take<double>(hg.size());
+        di = cv.take<int32_t>(hi_.size());
+        db = cv.take<double>(hb.size());
+        dt = cv.take<KdNode>(tree.size());
+        dkeys = cv.take<int32_t>(4 * (int64_t)nk);
+        k1 = cv.take<uint32_t>(n), k2 = cv.take<uint32_t>(n);
+        v1 = cv.take<int32_t>(n), v2 = cv.take<int32_t>(n), kslot = cv.take<int32_t>(n);
+        sort_tmp = cv.take<char>(tb);
+    });
+    int32_t *droot = dkeys + nk, *dglo = droot + nk, *dghi = dglo + nk;
     std::vector<int32_t> ktab((size_t)4 * nk);
     std::copy(keys.begin(), keys.end(), ktab.begin());
     std::copy(roots.begin(), roots.end(), ktab.begin() + nk);
@@ -522,7 +516,6 @@ static bool nearest_grouped(hdb_ctx *ctx, const double *X, int64_t n, const doub
     HIP_CHECK(hipMemcpyAsync(dg, hg.data(), sizeof(double) * hg.size(), hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(di, hi_.data(), 4 * hi_.size(), hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(db, hb.data(), 8 * hb.size(), hipMemcpyHostToDevice, st));
-    double *dsb = (double *)(base + o_sb);
     HIP_CHECK(hipMemcpyAsync(dsb, hsb.data(), 8 * hsb.size(), hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(dt, tree.data(), sizeof(KdNode) * tree.size(), hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(dkeys, ktab.data(), 4 * ktab.size(), hipMemcpyHostToDevice, st));
@@ -530,7 +523,7 @@ static bool nearest_grouped(hdb_ctx *ctx, const double *X, int64_t n, const doub
     const int g = (int)std::min<int64_t>(ceil_div(n, 256), 8192);
     hipLaunchKernelGGL(nng_home_kernel, dim3(g), dim3(256), 0, st, X, n, d, dt, skey ? xkey : nullptr, dkeys, nk,
                        droot, k1, v1, kslot);
-    HIP_CHECK(sort_pairs((void *)(base + o_tmp), tb, k1, k2, v1, v2, n, 0, 32, st));
+    HIP_CHECK(sort_pairs((void *)sort_tmp, tb, k1, k2, v1, v2, n, 0, 32, st));
     const unsigned blocks = (unsigned)ceil_div(n, 256);
     const size_t lds_arg = (size_t)ng * 2 * d * 8 <= 65536 ? (size_t)ng * 2 * d * 8 : 0;
 #define NNG_CASE(DD, GG)                                                                                         \
@@ -559,13 +552,6 @@ void nearest_sample_device(hdb_ctx *ctx, const double *X, int64_t n, const doubl
     if (metric == HDB_METRIC_EUCLIDEAN &&
         nearest_grouped(ctx, X, n, S, m, d, keyed ? xkey : nullptr, keyed ? skey : nullptr, out_i, out_d))
         return;
-    // scratch carve
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        size_t o = off;
-        off += (bytes + 255) & ~size_t(255);
-        return o;
-    };
     int dp = (d + 1) & ~1;
     const bool fast = metric == HDB_METRIC_EUCLIDEAN && (d <= 6 || d == 8 || d == 16);
     int tiles = (int)ceil_div(n, fast ? 256 * (d <= 4 ? 4 : (d <= 8 ? 2 : 1)) : 256);
@@ -574,28 +560,25 @@ void nearest_sample_device(hdb_ctx *ctx, const double *X, int64_t n, const doubl
     if (keyed) SPL = 1;  // key ranges are small; one split keeps the lane ranges simple
     int64_t chunk = ceil_div(std::max<int64_t>(m, 1), SPL);
 
-    size_t o_xp = carve(sizeof(double) * n * dp), o_sp = carve(sizeof(double) * m * dp);
-    size_t o_pr = carve(sizeof(double) * n * SPL), o_pi = carve(sizeof(int32_t) * n * SPL);
-    size_t o_xk = carve(sizeof(int32_t) * n), o_sk = carve(sizeof(int32_t) * m);
-    size_t o_xperm = carve(sizeof(int32_t) * n), o_sperm = carve(sizeof(int32_t) * m);
-    size_t o_tmp = carve(sizeof(int32_t) * std::max(n, m));
-    size_t o_xs = carve(sizeof(double) * n * d), o_ss = carve(sizeof(double) * m * d);
-    char *base = (char *)arena(ctx, A_WORK0, off);
-    double *Xp = (double *)(base + o_xp), *Sp = (double *)(base + o_sp);
-    double *pr = (double *)(base + o_pr);
-    int32_t *pi = (int32_t *)(base + o_pi);
+    // the arrays from kxk on are used by keyed calls only
+    double *Xp, *Sp, *pr, *Xs, *Ss;
+    int32_t *pi, *kxk, *ksk, *kxperm, *ksperm, *tmp;
+    carve(ctx, A_WORK0, [&](Carver &cv) {
+        Xp = cv.take<double>(n * dp), Sp = cv.take<double>(m * dp);
+        pr = cv.take<double>(n * SPL);
+        pi = cv.take<int32_t>(n * SPL);
+        kxk = cv.take<int32_t>(n), ksk = cv.take<int32_t>(m);
+        kxperm = cv.take<int32_t>(n), ksperm = cv.take<int32_t>(m);
+        tmp = cv.take<int32_t>(std::max(n, m));
+        Xs = cv.take<double>(n * d), Ss = cv.take<double>(m * d);
+    });
     int32_t *xks = nullptr, *sks = nullptr, *xperm = nullptr, *sperm = nullptr;
     const double *Xsrc = X, *Ssrc = S;
     int g = 1024;
     if (keyed) {
-        xks = (int32_t *)(base + o_xk);
-        sks = (int32_t *)(base + o_sk);
-        xperm = (int32_t *)(base + o_xperm);
-        sperm = (int32_t *)(base + o_sperm);
-        int32_t *tmp = (int32_t *)(base + o_tmp);
+        xks = kxk, sks = ksk, xperm = kxperm, sperm = ksperm;
         stable_sort_by_key(ctx, xkey, n, xks, xperm, tmp);
         stable_sort_by_key(ctx, skey, m, sks, sperm, tmp);
-        double *Xs = (double *)(base + o_xs), *Ss = (double *)(base + o_ss);
         hipLaunchKernelGGL(gather_rows_kernel, dim3(g), dim3(256), 0, ctx->stream, X, xperm, n, d, Xs);
         if (m) hipLaunchKernelGGL(gather_rows_kernel, dim3(g), dim3(256), 0, ctx->stream, S, sperm, m, d, Ss);
         Xsrc = Xs;

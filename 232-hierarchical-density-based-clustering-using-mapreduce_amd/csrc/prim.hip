@@ -822,14 +822,18 @@ static bool launch_coop4_bs(hdb_ctx *ctx, const PrimIn &in, int64_t o, int64_t n
     const int per_cu = coop_per_cu(ctx, (const void *)prim_coop4_kernel<BS, DM>, BS, nwg);
     if (!per_cu) return false;
     constexpr int ND = DM + 3;
-    const size_t kbytes = (8 * (size_t)3 * 2 * nwg + 255) & ~size_t(255);
-    const size_t rbytes = (8 * (size_t)2 * ND * 2 * nwg + 255) & ~size_t(255);
-    char *base = (char *)arena(ctx, A_WORK3, kbytes + rbytes + 512);
-    gu64 *gkey = (gu64 *)base;
-    gu64 *grow = (gu64 *)(base + kbytes);
-    int *err = (int *)(base + kbytes + rbytes);
+    char *state;
+    gu64 *gkey, *grow;
+    int *err;
+    const size_t state_bytes = carve(ctx, A_WORK3, [&](Carver &cv) {
+        state = cv.base;
+        gkey = (gu64 *)cv.take<unsigned long long>(3 * 2 * nwg);
+        grow = (gu64 *)cv.take<unsigned long long>(2 * ND * 2 * nwg);
+        err = cv.take<int>(128);
+        return cv.off;
+    });
     int *xcc = err + 64;  // the working blocks' XCC ids (spread launch)
-    HIP_CHECK(hipMemsetAsync(base, 0, kbytes + rbytes + 512, ctx->stream));  // tags 0: no step yet
+    HIP_CHECK(hipMemsetAsync(state, 0, state_bytes, ctx->stream));  // tags 0: no step yet
     PrimIn L = partition_slice(in, o);
     int nn = (int)n;
     int32_t *pva = va + eo, *pvb = vb + eo;
@@ -852,7 +856,7 @@ static bool launch_coop4_bs(hdb_ctx *ctx, const PrimIn &in, int64_t o, int64_t n
     const unsigned plain_spin = 1u << ctx->prim_coop_plain_spin_log2;
     int h_err = 0;
     for (int attempt = ctx->prim_coop_plain ? 0 : 1; attempt < 2; attempt++) {
-        if (attempt == 1 && h_err) HIP_CHECK(hipMemsetAsync(base, 0, kbytes + rbytes + 512, ctx->stream));
+        if (attempt == 1 && h_err) HIP_CHECK(hipMemsetAsync(state, 0, state_bytes, ctx->stream));
         {
             KernelTimer t(ctx, "prim_coop");
             if (attempt == 0)
@@ -968,14 +972,6 @@ void prim_batched_device(hdb_ctx *ctx, const PrimIn &in, const int64_t *h_offs, 
         if (c == 3 && in.d >= 8 && in.d <= 16 && ctx->prim_coop && ctx->prim_coop_slots == 4) c = 4;
         if (n > 0) cls[c].push_back(p);
     }
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        size_t o = off;
-        off += (bytes + 255) & ~size_t(255);
-        return o;
-    };
-    size_t o_off = carve(sizeof(int64_t) * (P + 1)), o_eoff = carve(sizeof(int64_t) * (P + 1));
-    size_t o_parts = carve(sizeof(int32_t) * (P + 1));
     // cooperative single-launch Prim for 4096 < n <= 65536 when the device allows it
     if (ctx->prim_coop) {
         std::vector<int32_t> rest;
@@ -1004,19 +1000,21 @@ void prim_batched_device(hdb_ctx *ctx, const PrimIn &in, const int64_t *h_offs, 
         for (int q = 0; q < c; q++) wg_part.push_back(p);
     }
     int nwg = (int)wg_part.size();
-    size_t o_wgp = carve(sizeof(int32_t) * (nwg + 1)), o_wgf = carve(sizeof(int32_t) * (P + 1)),
-           o_wgc = carve(sizeof(int32_t) * (P + 1));
-    size_t o_best = 0, o_par = 0, o_att = 0, o_pv = 0, o_pi = 0;
-    if (nwg) {
-        o_best = carve(sizeof(double) * total_v);
-        o_par = carve(sizeof(int32_t) * total_v);
-        o_att = carve(total_v);
-        o_pv = carve(sizeof(double) * 2 * nwg);
-        o_pi = carve(sizeof(int32_t) * 2 * nwg);
-    }
-    char *base = (char *)arena(ctx, A_WORK1, off);
-    int64_t *d_off = (int64_t *)(base + o_off), *d_eoff = (int64_t *)(base + o_eoff);
-    int32_t *d_parts = (int32_t *)(base + o_parts);
+    int64_t *d_off, *d_eoff;
+    int32_t *d_parts, *d_wgp, *d_wgf, *d_wgc;
+    StepState st{};
+    carve(ctx, A_WORK1, [&](Carver &cv) {
+        d_off = cv.take<int64_t>(P + 1), d_eoff = cv.take<int64_t>(P + 1);
+        d_parts = cv.take<int32_t>(P + 1);
+        d_wgp = cv.take<int32_t>(nwg + 1), d_wgf = cv.take<int32_t>(P + 1), d_wgc = cv.take<int32_t>(P + 1);
+        if (nwg) {
+            st.best = cv.take<double>(total_v);
+            st.par = cv.take<int32_t>(total_v);
+            st.att = cv.take<uint8_t>(total_v);
+            st.pv = cv.take<double>(2 * nwg);
+            st.pidx = cv.take<int32_t>(2 * nwg);
+        }
+    });
     std::vector<int64_t> rel(P + 1);
     for (int p = 0; p <= P; p++) rel[p] = h_offs[p] - h_offs[0];
     HIP_CHECK(hipMemcpyAsync(d_off, rel.data(), sizeof(int64_t) * (P + 1), hipMemcpyHostToDevice, ctx->stream));
@@ -1035,18 +1033,9 @@ void prim_batched_device(hdb_ctx *ctx, const PrimIn &in, const int64_t *h_offs, 
     launch_block<256, 4>(ctx, in, d_off, d_eoff, d_parts + cstart[2], (int)cls[2].size(), self_edges, va, vb, w);
     launch_block<1024, 4>(ctx, in, d_off, d_eoff, d_parts + cstart[3], (int)cls[3].size(), self_edges, va, vb, w);
     if (nwg) {
-        int32_t *d_wgp = (int32_t *)(base + o_wgp), *d_wgf = (int32_t *)(base + o_wgf),
-                *d_wgc = (int32_t *)(base + o_wgc);
         HIP_CHECK(hipMemcpyAsync(d_wgp, wg_part.data(), sizeof(int32_t) * nwg, hipMemcpyHostToDevice, ctx->stream));
         HIP_CHECK(hipMemcpyAsync(d_wgf, wg_first.data(), sizeof(int32_t) * P, hipMemcpyHostToDevice, ctx->stream));
         HIP_CHECK(hipMemcpyAsync(d_wgc, wg_count.data(), sizeof(int32_t) * P, hipMemcpyHostToDevice, ctx->stream));
-        StepState st;
-        st.best = (double *)(base + o_best);
-        st.par = (int32_t *)(base + o_par);
-        st.att = (uint8_t *)(base + o_att);
-        st.pv = (double *)(base + o_pv);
-        st.pidx = (int32_t *)(base + o_pi);
-        st.cur0 = nullptr;
         hipLaunchKernelGGL(prim_step_init_kernel, dim3(1024), dim3(256), 0, ctx->stream, d_off, P, st.best, st.par,
                            st.att, total_v);
         int64_t maxn = 0;

@@ -1853,20 +1853,8 @@ static Bvh bvh_shape(int64_t ntiles) {
     return bvh;
 }
 
-// bump allocator over one arena slot: pass 1 sizes (base == nullptr), pass 2 assigns
-struct Carve {
-    char *base = nullptr;
-    size_t off = 0;
-    template <class T>
-    T *take(size_t count) {
-        size_t o = off;
-        off += (sizeof(T) * count + 255) & ~size_t(255);
-        return base ? (T *)(base + o) : nullptr;
-    }
-};
-
 template <int D>
-static void spatial_carve(Carve &cv, Spatial<D> &sp) {
+static void spatial_carve(Carver &cv, Spatial<D> &sp) {
     const int64_t n = sp.n, nnodes = sp.bvh.off[sp.bvh.levels];
     sp.bvh.lo = cv.take<double>((size_t)D * nnodes);
     sp.bvh.hi = cv.take<double>((size_t)D * nnodes);
@@ -1882,10 +1870,10 @@ static void spatial_carve(Carve &cv, Spatial<D> &sp) {
     sp.perm = cv.take<int32_t>(n);
 }
 
-// Builds the index on ctx->stream.  core nullable (records then carry 0).  `extra` = bytes
-// the caller wants carved after the index in the same arena slot (returned in *extra_ptr).
+// Builds the index on ctx->stream.  core nullable (records then carry 0).  On a probing carver
+// (no base) it only takes its arrays.
 template <int D>
-static Spatial<D> build_spatial(hdb_ctx *ctx, const double *X, int64_t n, const double *core, Carve &cv) {
+static Spatial<D> build_spatial(hdb_ctx *ctx, const double *X, int64_t n, const double *core, Carver &cv) {
     if (n > INT32_MAX / 2) HDB_THROW(HDB_EINVAL, "n too large");
     Spatial<D> sp;
     sp.n = n;
@@ -1906,11 +1894,8 @@ static Spatial<D> build_spatial(hdb_ctx *ctx, const double *X, int64_t n, const 
               RecEmitF<D>{X, core, sp.recs, sp.inv}, st);
     } else {
         hipLaunchKernelGGL(morton_kernel, dim3(g), dim3(256), 0, st, X, n, D, blo, bhi, sp.keys, sp.iota);
-        size_t tb = 0;
         const int kbits = (D < 8 ? D : 8) * morton_bits(D);
-        HIP_CHECK(sort_pairs(nullptr, tb, sp.keys, sp.keys2, sp.iota, sp.perm, n, 0, kbits, st));
-        void *tmp = arena(ctx, A_SORT, tb);
-        HIP_CHECK(sort_pairs(tmp, tb, sp.keys, sp.keys2, sp.iota, sp.perm, n, 0, kbits, st));
+        sort_pairs(ctx, A_SORT, sp.keys, sp.keys2, sp.iota, sp.perm, n, 0, kbits);
         hipLaunchKernelGGL(build_recs_kernel<D>, dim3(g), dim3(256), 0, st, X, core, sp.perm, n, sp.recs, sp.inv);
     }
     hipLaunchKernelGGL(tile_box_kernel<D>, dim3((unsigned)sp.ntiles), dim3(64), 0, st, sp.recs, n, sp.bvh.lo,
@@ -1923,26 +1908,22 @@ static Spatial<D> build_spatial(hdb_ctx *ctx, const double *X, int64_t n, const 
     return sp;
 }
 
-template <int D>
-static Spatial<D> build_spatial_in(hdb_ctx *ctx, int slot, const double *X, int64_t n, const double *core,
-                                   Carve &cv, size_t extra_bytes, char **extra) {
-    Carve probe;
-    build_spatial<D>(ctx, X, n, core, probe);
-    char *base = (char *)arena(ctx, slot, probe.off + extra_bytes + 256);
-    cv.base = base;
-    cv.off = 0;
-    Spatial<D> sp = build_spatial<D>(ctx, X, n, core, cv);
-    if (extra) *extra = base + ((cv.off + 255) & ~size_t(255));
-    return sp;
+// the index first, then what the caller's layout `rest` takes after it, in one arena slot
+template <int D, class F>
+static Spatial<D> build_spatial_in(hdb_ctx *ctx, int slot, const double *X, int64_t n, const double *core, F &&rest) {
+    return carve(ctx, slot, [&](Carver &cv) {
+        Spatial<D> sp = build_spatial<D>(ctx, X, n, core, cv);
+        rest(cv);
+        return sp;
+    });
 }
 
 // ------------------------------------------------------------------- K1t host
 template <int D, int K>
 static void knn_tree_impl(hdb_ctx *ctx, const double *X, int64_t n, bool excl, double *lists) {
-    Carve cv;
-    char *extra = nullptr;
-    Spatial<D> sp = build_spatial_in<D>(ctx, A_WORK1, X, n, nullptr, cv, 64, &extra);
-    unsigned long long *evals = ctx->count_evals ? (unsigned long long *)extra : nullptr;
+    unsigned long long *evals;
+    Spatial<D> sp = build_spatial_in<D>(ctx, A_WORK1, X, n, nullptr, [&](Carver &cv) { evals = cv.take<unsigned long long>(3); });
+    if (!ctx->count_evals) evals = nullptr;
     if (evals) HIP_CHECK(hipMemsetAsync(evals, 0, 24, ctx->stream));
     {
         KernelTimer t(ctx, "knn_tree");
@@ -1993,20 +1974,6 @@ bool knn_tree_device(hdb_ctx *ctx, const double *X, int64_t n, int d, int KC, bo
 }
 
 // ------------------------------------------------------------------- K2b host
-// per-round Boruvka state carved after the index: comp_w, comp_key, comp_s, best_w, best_s
-// (8n each), best_lo/hi, parent, parent2 (4n each), counters, edge lists
-// diag: count_evals -- one BOR_STATS_REC-word record per scan wave, sized for the most waves a
-// round can have (16 points per wave: boruvka_wave_pts / boruvka_early_pts may ask for it)
-static size_t boruvka_extra_bytes(int64_t n, bool diag) {
-    const size_t per = (size_t)n;
-    auto rnd = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t waves_max = (size_t)ceil_div(n, (int64_t)WGRP) * (WGRP / 16);
-    return 5 * rnd(8 * per) + 5 * rnd(4 * per) + 3 * 256 + 2 * rnd(4 * per) + rnd(8 * per) +
-           (diag ? rnd(8 * (size_t)BOR_STATS_REC * waves_max) : 0) +
-           rnd(4 * per) + 3 * rnd(4 * (per / WGRP + 1)) + rnd(8 * waves_max) + 256 +  // + work lists
-           2 * rnd(4 * per) + 2 * rnd(8 * per) + rnd(per);  // + best_pos, pcomp, lbw, cap, xact
-}
-
 // k-NN lists over the index's sorted positions (K1t with IDX): candidates of the first
 // leaf_list_rounds Boruvka rounds, lower bounds of every round (round_seed_kernel)
 struct KnnLists {
@@ -2016,13 +1983,7 @@ struct KnnLists {
     uint8_t *done = nullptr;  // n flags: the lane's seed is exact this round
 };
 
-// Boruvka rounds over a built index whose records carry the core distances.  extra: the
-// boruvka_extra_bytes(n) region.  kl (nullable): k-NN lists that seed and bound the rounds.
-template <int D>
-static void boruvka_on_index(hdb_ctx *ctx, Spatial<D> &sp, int64_t n, char *extra, const KnnLists *kl,
-                             int32_t *va, int32_t *vb, double *w, bool merged = false,
-                             const double *self_core = nullptr);
-
+// the Boruvka rounds' state, carved after the index (boruvka_carve)
 template <int D>
 struct BoruvkaState {
     unsigned long long *comp_w, *comp_key, *comp_s;
@@ -2033,13 +1994,27 @@ struct BoruvkaState {
     double *lbw;        // per point: lower bound of its best outgoing weight (monotone over rounds)
     uint8_t *xact;      // per point: best_* is the exact best of the last round
     double *cap;        // per point: max(fl(sqrt(s_K)), core) of a full k-NN list, else +0.0 (round_seed_kernel)
+    int32_t *parent, *parent2, *ea, *eb;  // hook forest, edge list
+    double *ew;
+    unsigned long long *n_edges;
+    int32_t *work, *gcnt, *gwaves, *woff, *nwaves;  // the scan's work lists per WGRP-point group
+    unsigned long long *desc;
+    unsigned long long *evals;  // count_evals: one BOR_STATS_REC-word record per scan wave
+    int P, PE;                  // points per scan wave, late and early rounds
+    int64_t ngroups, max_waves;  // the most waves a round can have
 };
 template <int D>
-static BoruvkaState<D> boruvka_state(char *extra, int64_t n, size_t *used = nullptr) {
-    Carve ex;
-    ex.base = extra;
-    const size_t per = (size_t)n;
+static BoruvkaState<D> boruvka_carve(Carver &ex, hdb_ctx *ctx, int64_t n) {
+    const int64_t per = n;
     BoruvkaState<D> b;
+    b.P = ctx->boruvka_wave_pts;
+    if (b.P != 16 && b.P != 32 && b.P != 64) HDB_THROW(HDB_EINVAL, "boruvka_wave_pts must be 16, 32 or 64");
+    // early rounds search few lanes (few waves in flight for a latency-bound walk): optionally
+    // spread their work over more, smaller waves
+    b.PE = ctx->boruvka_early_pts ? ctx->boruvka_early_pts : b.P;
+    if (b.PE != 16 && b.PE != 32 && b.PE != 64) HDB_THROW(HDB_EINVAL, "boruvka_early_pts must be 16, 32 or 64");
+    b.ngroups = ceil_div(n, (int64_t)WGRP);
+    b.max_waves = b.ngroups * (WGRP / std::min(b.P, b.PE));
     b.best_w = ex.take<double>(per);
     b.best_s = ex.take<double>(per);
     b.best_lo = ex.take<int32_t>(per);
@@ -2052,52 +2027,48 @@ static BoruvkaState<D> boruvka_state(char *extra, int64_t n, size_t *used = null
     b.lbw = ex.take<double>(per);
     b.xact = ex.take<uint8_t>(per);
     b.cap = ex.take<double>(per);
-    if (used) *used = ex.off;
+    b.parent = ex.take<int32_t>(per), b.parent2 = ex.take<int32_t>(per);
+    b.n_edges = ex.take<unsigned long long>(1);
+    b.ea = ex.take<int32_t>(per), b.eb = ex.take<int32_t>(per);
+    b.ew = ex.take<double>(per);
+    b.work = ex.take<int32_t>(per);
+    b.gcnt = ex.take<int32_t>(b.ngroups), b.gwaves = ex.take<int32_t>(b.ngroups), b.woff = ex.take<int32_t>(b.ngroups);
+    b.desc = ex.take<unsigned long long>(b.max_waves);
+    b.nwaves = ex.take<int32_t>(1);
+    b.evals = ctx->count_evals ? ex.take<unsigned long long>((int64_t)BOR_STATS_REC * b.max_waves) : nullptr;
     return b;
 }
+
+// Boruvka rounds over a built index whose records carry the core distances.  kl (nullable):
+// k-NN lists that seed and bound the rounds.
+template <int D>
+static void boruvka_on_index(hdb_ctx *ctx, Spatial<D> &sp, int64_t n, const BoruvkaState<D> &bs, const KnnLists *kl,
+                             int32_t *va, int32_t *vb, double *w, bool merged = false,
+                             const double *self_core = nullptr);
 
 template <int D>
 static void boruvka_impl(hdb_ctx *ctx, const double *X, int64_t n, const double *core, int32_t *va, int32_t *vb,
                          double *w) {
-    Carve cv;
-    char *extra = nullptr;
     KernelTimer tt(ctx, "boruvka_total");
-    Spatial<D> sp = build_spatial_in<D>(ctx, A_WORK0, X, n, core, cv, boruvka_extra_bytes(n, ctx->count_evals), &extra);
-    boruvka_on_index<D>(ctx, sp, n, extra, nullptr, va, vb, w);
+    BoruvkaState<D> bs;
+    Spatial<D> sp = build_spatial_in<D>(ctx, A_WORK0, X, n, core, [&](Carver &cv) { bs = boruvka_carve<D>(cv, ctx, n); });
+    boruvka_on_index<D>(ctx, sp, n, bs, nullptr, va, vb, w);
 }
 
 template <int D>
-static void boruvka_on_index(hdb_ctx *ctx, Spatial<D> &sp, int64_t n, char *extra, const KnnLists *kl,
+static void boruvka_on_index(hdb_ctx *ctx, Spatial<D> &sp, int64_t n, const BoruvkaState<D> &bs, const KnnLists *kl,
                              int32_t *va, int32_t *vb, double *w, bool merged, const double *self_core) {
     const size_t per = (size_t)n;
-    size_t used = 0;
-    BoruvkaState<D> bs = boruvka_state<D>(extra, n, &used);
-    Carve ex;  // the rest of the region, after the BoruvkaState arrays
-    ex.base = extra;
-    ex.off = used;
     unsigned long long *comp_w = bs.comp_w, *comp_key = bs.comp_key, *comp_s = bs.comp_s;
     double *best_w = bs.best_w, *best_s = bs.best_s;
     int32_t *best_lo = bs.best_lo, *best_hi = bs.best_hi;
-    int32_t *parent = ex.take<int32_t>(per), *parent2 = ex.take<int32_t>(per);
-    unsigned long long *n_edges = ex.take<unsigned long long>(1);
-    int32_t *ea = ex.take<int32_t>(per), *eb = ex.take<int32_t>(per);
-    double *ew = ex.take<double>(per);
+    int32_t *parent = bs.parent, *parent2 = bs.parent2, *ea = bs.ea, *eb = bs.eb;
+    double *ew = bs.ew;
+    unsigned long long *n_edges = bs.n_edges, *desc = bs.desc, *evals = bs.evals;
+    int32_t *work = bs.work, *gcnt = bs.gcnt, *gwaves = bs.gwaves, *woff = bs.woff, *nwaves = bs.nwaves;
+    const int P = bs.P, PE = bs.PE;
+    const int64_t ngroups = bs.ngroups, max_waves = bs.max_waves;
     std::vector<unsigned long long> wave_cyc(ctx->count_evals ? sp.ntiles : 0);
-    const int64_t ngroups = ceil_div(n, (int64_t)WGRP);
-    const int P = ctx->boruvka_wave_pts;
-    if (P != 16 && P != 32 && P != 64) HDB_THROW(HDB_EINVAL, "boruvka_wave_pts must be 16, 32 or 64");
-    // early rounds search few lanes (few waves in flight for a latency-bound walk): optionally
-    // spread their work over more, smaller waves
-    const int PE = ctx->boruvka_early_pts ? ctx->boruvka_early_pts : P;
-    if (PE != 16 && PE != 32 && PE != 64) HDB_THROW(HDB_EINVAL, "boruvka_early_pts must be 16, 32 or 64");
-    const int64_t max_waves = ngroups * (WGRP / std::min(P, PE));
-    int32_t *work = ex.take<int32_t>(per);
-    int32_t *gcnt = ex.take<int32_t>(ngroups), *gwaves = ex.take<int32_t>(ngroups), *woff = ex.take<int32_t>(ngroups);
-    unsigned long long *desc = ex.take<unsigned long long>(max_waves);
-    int32_t *nwaves = ex.take<int32_t>(1);
-    unsigned long long *evals = ctx->count_evals ? ex.take<unsigned long long>((size_t)BOR_STATS_REC * max_waves) : nullptr;
-    if (ex.off > boruvka_extra_bytes(n, ctx->count_evals))
-        HDB_THROW(HDB_EINVAL, "boruvka: scratch carve exceeds its reserve");
     int64_t tot_evals = 0;
     Rec<D> *recs = sp.recs;
     int32_t *inv = sp.inv;
@@ -2188,10 +2159,9 @@ static void boruvka_on_index(hdb_ctx *ctx, Spatial<D> &sp, int64_t n, char *extr
                 hipLaunchKernelGGL(adj_seed_kernel<D>, dim3(g), dim3(256), 0, st, recs, pcomp, n, comp_w);
             hipLaunchKernelGGL(group_compact_kernel<D>, dim3((unsigned)ngroups), dim3(WGRP), 0, st, recs, n,
                                kl ? kl->done : nullptr, bs.lbw, comp_w, Pr, work, gcnt, gwaves);
-            size_t tb = 0;
-            HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, gwaves, woff, (int)ngroups, st));
-            void *tmp = arena(ctx, A_SORT, tb);
-            HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, gwaves, woff, (int)ngroups, st));
+            with_tmp(ctx, A_SORT, [&](void *tmp, size_t &tb) {
+                return hipcub::DeviceScan::ExclusiveSum(tmp, tb, gwaves, woff, (int)ngroups, st);
+            });
             hipLaunchKernelGGL(wave_desc_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(ngroups, 256), 4096)),
                                dim3(256), 0, st, gcnt, woff, ngroups, Pr, desc, nwaves);
             const int xm = ctx->bor_xcd_chunks > 0 ? ctx->bor_xcd_chunks : 0;
@@ -2325,16 +2295,11 @@ static void boruvka_on_index(hdb_ctx *ctx, Spatial<D> &sp, int64_t n, char *extr
             int B = 1;
             while (B < 31 && ((int64_t)1 << B) < n) B++;
             hipLaunchKernelGGL(edge_idkey_kernel, dim3(g), dim3(256), 0, st, ea, eb, ne, B, k1, p1);
-            size_t tb = 0;
-            HIP_CHECK(sort_pairs(nullptr, tb, k1, k2, p1, p2, ne, 0, 2 * B, st));
-            void *tmp = arena(ctx, A_SORT, tb);
-            HIP_CHECK(sort_pairs(tmp, tb, k1, k2, p1, p2, ne, 0, 2 * B, st));
+            sort_pairs(ctx, A_SORT, k1, k2, p1, p2, ne, 0, 2 * B);
             hipLaunchKernelGGL(edge_wkey_kernel, dim3(g), dim3(256), 0, st, p2, ew, ne, k1);
             if (!merged) {
                 // stable sort by w (non-negative doubles: bit order == numeric order, sign bit 0)
-                HIP_CHECK(sort_pairs(nullptr, tb, k1, k2, p2, p1, ne, 0, 63, st));
-                tmp = arena(ctx, A_SORT, tb);
-                HIP_CHECK(sort_pairs(tmp, tb, k1, k2, p2, p1, ne, 0, 63, st));
+                sort_pairs(ctx, A_SORT, k1, k2, p2, p1, ne, 0, 63);
                 hipLaunchKernelGGL(edge_out_kernel, dim3(g), dim3(256), 0, st, p1, ea, eb, ew, ne, va, vb, w);
                 HIP_CHECK(hipGetLastError());
             } else {
@@ -2343,28 +2308,22 @@ static void boruvka_on_index(hdb_ctx *ctx, Spatial<D> &sp, int64_t n, char *extr
                 // order -- exactly how a stable descending sort keeps FirstStep's (w, lo, hi)
                 // tie groups -- then merged with the self edges sorted by core (descending, ids
                 // ascending on ties), tree edges first on equal weights.  No 2n-1 re-sort.
-                HIP_CHECK(sort_pairs_desc(nullptr, tb, k1, k2, p2, p1, ne, 0, 63, st));
-                tmp = arena(ctx, A_SORT, tb);
-                HIP_CHECK(sort_pairs_desc(tmp, tb, k1, k2, p2, p1, ne, 0, 63, st));
+                sort_pairs_desc(ctx, A_SORT, k1, k2, p2, p1, ne, 0, 63);
                 if (!self_core) {
                     hipLaunchKernelGGL(edge_out_kernel, dim3(g), dim3(256), 0, st, p1, ea, eb, ew, ne, va, vb, w);
                     HIP_CHECK(hipGetLastError());
                 } else {
-                    auto rnd = [](size_t b) { return (b + 255) & ~size_t(255); };
-                    const size_t o_tb = rnd(4 * (size_t)ne), o_tw = o_tb + rnd(4 * (size_t)ne),
-                                 o_sk = o_tw + rnd(8 * (size_t)ne), o_sk2 = o_sk + rnd(8 * (size_t)n),
-                                 o_si = o_sk2 + rnd(8 * (size_t)n), o_sp = o_si + rnd(4 * (size_t)n),
-                                 tot = o_sp + rnd(4 * (size_t)n);
-                    char *base = (char *)arena(ctx, A_WORK3, tot);
-                    int32_t *ta = (int32_t *)base, *tbv = (int32_t *)(base + o_tb);
-                    double *tw = (double *)(base + o_tw), *sk = (double *)(base + o_sk), *sk2 = (double *)(base + o_sk2);
-                    int32_t *si = (int32_t *)(base + o_si), *sperm = (int32_t *)(base + o_sp);
+                    int32_t *ta, *tbv, *si, *sperm;
+                    double *tw, *sk, *sk2;
+                    carve(ctx, A_WORK3, [&](Carver &cv) {
+                        ta = cv.take<int32_t>(ne), tbv = cv.take<int32_t>(ne);
+                        tw = cv.take<double>(ne);
+                        sk = cv.take<double>(n), sk2 = cv.take<double>(n);
+                        si = cv.take<int32_t>(n), sperm = cv.take<int32_t>(n);
+                    });
                     hipLaunchKernelGGL(edge_out_kernel, dim3(g), dim3(256), 0, st, p1, ea, eb, ew, ne, ta, tbv, tw);
                     hipLaunchKernelGGL(self_keys_kernel, dim3(g), dim3(256), 0, st, self_core, n, sk, si);
-                    size_t tb2 = 0;
-                    HIP_CHECK(sort_pairs_desc(nullptr, tb2, sk, sk2, si, sperm, n, 0, 64, st));
-                    void *tmp2 = arena(ctx, A_SORT, tb2);
-                    HIP_CHECK(sort_pairs_desc(tmp2, tb2, sk, sk2, si, sperm, n, 0, 64, st));
+                    sort_pairs_desc(ctx, A_SORT, sk, sk2, si, sperm, n, 0, 64);
                     hipLaunchKernelGGL(gather_core_kernel, dim3(g), dim3(256), 0, st, self_core, sperm, n, sk2);
                     merge_two_runs_device(ctx, ta, tbv, tw, ne, sperm, sperm, sk2, n, va, vb, w);
                 }
@@ -2400,20 +2359,21 @@ template <int D, int K>
 static void exact_leaf_impl(hdb_ctx *ctx, const double *X, int64_t n, int min_pts, int semantics, double *core,
                             int self_edges, int32_t *va, int32_t *vb, double *w) {
     KernelTimer tt(ctx, "exact_leaf_total");
-    auto rnd = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t bx = rnd(boruvka_extra_bytes(n, ctx->count_evals));
-    const size_t nk = (size_t)n * K;
-    const size_t more = rnd(8 * nk) + rnd(4 * nk) + rnd(8 * nk) + rnd((size_t)n) + 256;
-    Carve cv;
-    char *extra = nullptr;
-    Spatial<D> sp = build_spatial_in<D>(ctx, A_WORK0, X, n, nullptr, cv, bx + more, &extra);
-    Carve ex;
-    ex.base = extra + bx;
-    double *lists = ex.take<double>(nk);
-    int32_t *nb_pos = ex.take<int32_t>(nk);
-    double *nb_s = ex.take<double>(nk);
-    uint8_t *done = ex.take<uint8_t>((size_t)n);
-    unsigned long long *stats = ctx->count_evals ? ex.take<unsigned long long>(3) : nullptr;
+    const int64_t nk = n * K;
+    BoruvkaState<D> bs;
+    double *lists, *nb_s;
+    int32_t *nb_pos;
+    uint8_t *done;
+    unsigned long long *stats;
+    // one index, then the Boruvka state, then the k-NN lists
+    Spatial<D> sp = build_spatial_in<D>(ctx, A_WORK0, X, n, nullptr, [&](Carver &cv) {
+        bs = boruvka_carve<D>(cv, ctx, n);
+        lists = cv.take<double>(nk);
+        nb_pos = cv.take<int32_t>(nk);
+        nb_s = cv.take<double>(nk);
+        done = cv.take<uint8_t>(n);
+        stats = ctx->count_evals ? cv.take<unsigned long long>(3) : nullptr;
+    });
     if (stats) HIP_CHECK(hipMemsetAsync(stats, 0, 24, ctx->stream));
     {
         KernelTimer t(ctx, "knn_tree");
@@ -2445,7 +2405,7 @@ static void exact_leaf_impl(hdb_ctx *ctx, const double *X, int64_t n, int min_pt
     const bool self = self_edges & HDB_EDGES_SELF, merged = self_edges & HDB_EDGES_MERGED;
     {
         KernelTimer tb(ctx, "boruvka_total");
-        boruvka_on_index<D>(ctx, sp, n, extra, ctx->boruvka_knn_seed ? &kl : nullptr, va, vb, w, merged,
+        boruvka_on_index<D>(ctx, sp, n, bs, ctx->boruvka_knn_seed ? &kl : nullptr, va, vb, w, merged,
                             (merged && self) ? core : nullptr);
     }
     if (self && !merged) self_edges_device(ctx, core, n, va + (n - 1), vb + (n - 1), w + (n - 1));

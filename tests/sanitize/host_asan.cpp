@@ -1,13 +1,15 @@
 // ASan/UBSan driver for the product's host C++: csrc/flat.cpp (global flat
 // labels), csrc/formats.cpp (record formats), csrc/local_model.cpp (bubble core epilogue,
 // UndirectedGraph quicksort, cluster tree, FOSC + noise reassignment), csrc/inf_edges.cpp (the
-// exact leaf's infinite-weight tail, against an all-pairs Kruskal).  Built by
+// exact leaf's infinite-weight tail, against an all-pairs Kruskal), and common.hpp's Carver (the
+// bump allocator every device scratch layout goes through).  Built by
 // tests/sanitize/Makefile (hipcc --cuda-host-only -fsanitize=address,undefined) and run by
 // tests/test_sanitizers.py on tie-heavy seeded inputs and malformed records.  The library's
 // error setter lives in context.cpp (HIP runtime); a host stub stands in for it here.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -235,7 +237,64 @@ static bool inf_tail() {
     return true;
 }
 
+// common.hpp's Carver: a layout of mixed types and counts (0 and 1 among them) run once on a null
+// base and once on a malloc(off) buffer gives the same offsets, 256-byte aligned, pairwise disjoint
+// ranges, the last one ending at off; every element of every range is then written (ASan: in bounds)
+static bool carver() {
+    struct Range {
+        size_t begin, bytes;
+    };
+    auto layout = [](hdb::Carver &cv, std::vector<Range> &r) {
+        auto note = [&](size_t before, size_t elem, int64_t count) {
+            r.push_back(Range{before, elem * (size_t)std::max<int64_t>(count, 1)});
+        };
+        const int64_t counts[] = {0, 1, 3, 64, 65, 257, 1000, 4097};
+        for (int64_t c : counts) {
+            size_t o = cv.off;
+            uint8_t *a = cv.take<uint8_t>(c);
+            note(o, 1, c);
+            o = cv.off;
+            int32_t *b = cv.take<int32_t>(c);
+            note(o, 4, c);
+            o = cv.off;
+            double *d = cv.take<double>(c);
+            note(o, 8, c);
+            struct Rec24 {
+                double x[3];
+            };
+            o = cv.off;
+            Rec24 *e = cv.take<Rec24>(c);
+            note(o, sizeof(Rec24), c);
+            if (cv.base) {  // write every element; the pointers are where the offsets say
+                const int64_t k = std::max<int64_t>(c, 1);
+                if ((char *)a != cv.base + r[r.size() - 4].begin || (char *)b != cv.base + r[r.size() - 3].begin ||
+                    (char *)d != cv.base + r[r.size() - 2].begin || (char *)e != cv.base + r[r.size() - 1].begin)
+                    return false;
+                for (int64_t i = 0; i < k; i++) a[i] = 1, b[i] = 2, d[i] = 3.0, e[i].x[2] = 4.0;
+            } else if (a || b || d || e) {
+                return false;  // a probing carver hands out no pointers
+            }
+        }
+        return true;
+    };
+    hdb::Carver probe;
+    std::vector<Range> pr, ar;
+    if (!layout(probe, pr)) return false;
+    hdb::Carver cv{(char *)malloc(probe.off)};
+    bool ok = layout(cv, ar) && cv.off == probe.off && pr.size() == ar.size();
+    for (size_t i = 0; ok && i < ar.size(); i++) {
+        ok = pr[i].begin == ar[i].begin && pr[i].bytes == ar[i].bytes && ar[i].begin % 256 == 0;
+        // bump order: a range ends at or before the next begins (so all are pairwise disjoint), the last at off
+        const size_t next = i + 1 < ar.size() ? ar[i + 1].begin : cv.off;
+        ok = ok && ar[i].begin + ar[i].bytes <= next && next - ar[i].begin == ((ar[i].bytes + 255) & ~size_t(255));
+    }
+    free(cv.base);
+    if (!ok) printf("Carver: probing and assigning passes disagree, or a range is misplaced\n");
+    return ok;
+}
+
 int main() {
+    if (!carver()) return 1;
     // K6 relabel limit (flat.hip): contracted labels nv + rank < 3m must fit int32
     if (!hdb::flat_relabel_fits(715827882) || hdb::flat_relabel_fits(715827883) || !hdb::flat_relabel_fits(0)) {
         printf("flat_relabel_fits limit wrong\n");

@@ -1,7 +1,8 @@
 """ASan/UBSan on the host code (SURVEY.md §5 "race detection / sanitizers"): the CPU oracle
 (oracle/hdb_oracle.c) and the product's host C++ (csrc/flat.cpp, formats.cpp,
 local_model.cpp, inf_edges.cpp) are rebuilt with -fsanitize=address,undefined by tests/sanitize/Makefile and
-driven over tie-heavy seeded inputs, error paths and malformed records.  A sanitizer report
+driven over tie-heavy seeded inputs, error paths and malformed records; host_asan also runs the
+scratch Carver of csrc/common.hpp (probing and assigning passes agree, every range written).  A sanitizer report
 aborts the driver (non-zero exit).  The same host code is also built with -fsanitize=thread and
 run from 8 threads at once (host_tsan: the C3/C5 local-model pool's host half), each thread's
 result digest checked against a serial run of its seed.  GPU sanitizers are not available on the GPU pool; the
