@@ -57,6 +57,68 @@ class NumberFormatException(HdbError):
 _EXC = {-10: NullPointerException, -11: ArrayIndexOutOfBoundsException, -12: IllegalStateException,
         -13: ArithmeticException, -14: NumberFormatException}
 
+_vp = C.c_void_p  # every array, handle and opaque pointer
+_i64, _i32, _int, _str = C.c_int64, C.c_int32, C.c_int, C.c_char_p
+# One row per function of include/hdbmi.h: name -> (restype, argtypes); _int as restype is a status.
+# lib() applies it, EXPORTED is its keys, and tests/test_capi.py compares every row with the header's
+# prototype.
+SIGNATURES = {
+    "hdb_ctx_create": (_int, [_int, C.POINTER(_vp)]),
+    "hdb_ctx_set_stream": (_int, [_vp, _vp]),
+    "hdb_ctx_set_timing": (_int, [_vp, _int]),
+    "hdb_ctx_kernel_time": (_int, [_vp, _str, C.POINTER(C.c_double), C.POINTER(_i64), _int]),
+    "hdb_ctx_synchronize": (_int, [_vp]),
+    "hdb_ctx_set_option": (_int, [_vp, _str, _i64]),
+    "hdb_ctx_get_stat": (_int, [_vp, _str, C.POINTER(_i64)]),
+    "hdb_distance_rows": (_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp]),
+    "hdb_core_distances": (_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "hdb_knn": (_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "hdb_prim_mst": (_int, [_vp, _vp, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "hdb_prim_mst_batched": (_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "hdb_leaf_msts": (_int, [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "hdb_mst_boruvka": (_int, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "hdb_exact_mst": (_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "hdb_nearest_sample": (_int, [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "hdb_attach_points": (_int, [_vp, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "hdb_attach_points_splits": (_int, [_vp, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "hdb_bubble_stats": (_int, [_vp, _vp, _i64, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "hdb_bubble_partials": (_int, [_vp, _vp, _i64, _i32, _vp, _i64, _vp, _i32, _vp, _vp, _vp]),
+    "hdb_bubble_combine": (_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "hdb_bubble_core_distances": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    "hdb_bubble_prim_mst": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "hdb_local_model": (_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hdb_local_model_cores": (_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     _vp, _vp, _vp]),
+    "hdb_quicksort_edges": (_int, [_vp, _vp, _vp, _i64]),
+    "hdb_sort_edges_desc": (_int, [_vp, _vp, _vp, _vp, _i64]),
+    "hdb_merge_sorted_runs": (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "hdb_flat_labels": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
+    "hdb_flat_outlier_scores": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "hdb_flat_cluster_tree": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     _vp, _vp, _vp, _vp]),
+    "hdb_labels_at_levels": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _vp]),
+    "hdb_predict_labels": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "hdb_constrained_flat_labels": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                                           _vp, _vp, _vp]),
+    "hdb_local_mst_ids": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "hdb_comm_unique_id": (_int, [_vp, _i32]),
+    "hdb_comm_init": (_int, [_vp, _i32, _i32, _vp, C.POINTER(_vp)]),
+    "hdb_free": (_int, [_vp]),
+    "hdb_copy": (_int, [_vp, _vp, _vp, _i64]),
+    "hdb_merge_edges": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
+                               C.POINTER(_i64)]),
+    "hdb_format_double": (_int, [C.c_double, _str, _i32]),
+    "hdb_parse_points": (_int, [_str, _i64, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "hdb_format_mst_records": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "hdb_parse_mst_records": (_int, [_str, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "hdb_last_error": (_str, []),
+    "hdb_version": (_int, []),
+    "hdb_ctx_destroy": (None, [_vp]),
+    "hdb_comm_destroy": (None, [_vp]),
+    "hdb_cluster_tree_bound": (_i64, [_i64, _i32]),
+}
+EXPORTED = list(SIGNATURES)
+
 _lib = None
 _lock = threading.Lock()
 
@@ -80,87 +142,22 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise ImportError(f"libhdbmi.so not built ({LIB_PATH}); run build_lib.py / __graft_entry__.build()")
         L = C.CDLL(LIB_PATH)
-        vp, dp, ip, lp = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p
-        i64, i32 = C.c_int64, C.c_int32
-        sig = {
-            "hdb_ctx_create": [C.c_int, C.POINTER(vp)],
-            "hdb_ctx_set_stream": [vp, vp],
-            "hdb_ctx_set_timing": [vp, C.c_int],
-            "hdb_ctx_kernel_time": [vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int],
-            "hdb_ctx_synchronize": [vp],
-            "hdb_ctx_set_option": [vp, C.c_char_p, C.c_int64],
-            "hdb_ctx_get_stat": [vp, C.c_char_p, C.POINTER(C.c_int64)],
-            "hdb_distance_rows": [vp, dp, dp, i64, i32, i32, dp],
-            "hdb_core_distances": [vp, dp, i64, i32, i32, i32, i32, dp],
-            "hdb_knn": [vp, dp, i64, i32, i32, i32, i32, dp, ip],
-            "hdb_prim_mst": [vp, dp, i64, i32, dp, ip, i32, i32, ip, ip, dp],
-            "hdb_prim_mst_batched": [vp, dp, lp, i32, i32, dp, ip, i32, i32, ip, ip, dp],
-            "hdb_leaf_msts": [vp, dp, lp, i32, i32, ip, i32, i32, dp, ip, ip, dp],
-            "hdb_mst_boruvka": [vp, dp, i64, i32, dp, i32, i32, ip, ip, dp],
-            "hdb_exact_mst": [vp, dp, i64, i32, i32, i32, i32, i32, dp, ip, ip, dp],
-            "hdb_nearest_sample": [vp, dp, i64, dp, i64, i32, i32, ip, ip, ip, dp],
-            "hdb_attach_points": [vp, dp, i64, i32, dp, dp, i64, i32, i32, dp, ip, dp],
-            "hdb_attach_points_splits": [vp, dp, i64, i32, dp, dp, i64, i32, i32, i32, dp, ip, dp],
-            "hdb_bubble_stats": [vp, dp, i64, i32, ip, i64, i32, dp, dp, dp, dp],
-            "hdb_bubble_partials": [vp, dp, i64, i32, ip, i64, lp, i32, dp, dp, dp],
-            "hdb_bubble_combine": [vp, dp, dp, dp, i32, i64, i32, dp, dp, dp, dp],
-            "hdb_bubble_core_distances": [vp, dp, ip, dp, dp, i64, i32, i32, i32, dp],
-            "hdb_bubble_prim_mst": [vp, dp, dp, dp, ip, dp, i64, i32, i32, i32, ip, ip, dp],
-            "hdb_local_model": [vp, dp, dp, i64, i32, i32, i32, i32, ip, ip, ip, dp, ip, ip, dp, lp],
-            "hdb_local_model_cores": [vp, dp, dp, i64, i32, i32, i32, i32, dp, ip, ip, ip, dp, ip, ip, dp, lp],
-            "hdb_quicksort_edges": [ip, ip, dp, i64],
-            "hdb_sort_edges_desc": [vp, ip, ip, dp, i64],
-            "hdb_merge_sorted_runs": [vp, ip, ip, dp, lp, i32, ip, ip, dp],
-            "hdb_flat_labels": [vp, ip, ip, dp, i64, i64, i32, ip, lp],
-            "hdb_flat_outlier_scores": [vp, ip, ip, dp, i64, i64, i32, dp, dp, ip, lp],
-            "hdb_flat_cluster_tree": [vp, ip, ip, dp, i64, i64, i32, i64, lp, ip, dp, dp, dp, ip, ip, ip, ip, dp, lp],
-            "hdb_labels_at_levels": [vp, ip, dp, i64, ip, dp, i64, dp, i32, ip],
-            "hdb_predict_labels": [vp, ip, dp, dp, ip, i64, ip, dp, i64, ip, dp, i64, ip, ip, dp],
-            "hdb_constrained_flat_labels": [vp, ip, dp, ip, i64, ip, i64, ip, ip, ip, i64, ip, ip, dp, ip, ip, lp],
-            "hdb_local_mst_ids": [vp, ip, i64, ip, ip, dp, i64, i32, ip, ip, ip],
-            "hdb_comm_unique_id": [vp, i32],
-            "hdb_comm_init": [vp, i32, i32, vp, C.POINTER(vp)],
-            "hdb_free": [vp],
-            "hdb_copy": [vp, vp, vp, i64],
-            "hdb_merge_edges": [vp, ip, ip, dp, lp, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
-                                C.POINTER(C.c_int64)],
-            "hdb_format_double": [C.c_double, C.c_char_p, i32],
-            "hdb_parse_points": [C.c_char_p, i64, i32, i32, dp, i64, lp, ip],
-            "hdb_format_mst_records": [ip, ip, dp, ip, ip, ip, i64, vp, i64, lp],
-            "hdb_parse_mst_records": [C.c_char_p, i64, ip, ip, dp, ip, ip, ip, i64, lp],
-        }
-        for name, args in sig.items():
+        for name, (restype, argtypes) in SIGNATURES.items():
             f = getattr(L, name)
-            f.argtypes = args
-            f.restype = C.c_int
-        L.hdb_ctx_destroy.argtypes = [vp]
-        L.hdb_ctx_destroy.restype = None
-        L.hdb_comm_destroy.argtypes = [vp]
-        L.hdb_comm_destroy.restype = None
-        L.hdb_last_error.restype = C.c_char_p
-        L.hdb_version.restype = C.c_int
-        L.hdb_cluster_tree_bound.argtypes = [i64, i32]
-        L.hdb_cluster_tree_bound.restype = i64
+            f.restype, f.argtypes = restype, argtypes
         _lib = L
     return _lib
-
-
-EXPORTED = ["hdb_ctx_create", "hdb_ctx_destroy", "hdb_ctx_set_stream", "hdb_ctx_set_timing", "hdb_ctx_set_option",
-            "hdb_ctx_get_stat", "hdb_ctx_kernel_time", "hdb_ctx_synchronize", "hdb_last_error", "hdb_version",
-            "hdb_distance_rows", "hdb_core_distances", "hdb_knn", "hdb_prim_mst", "hdb_prim_mst_batched",
-            "hdb_leaf_msts", "hdb_mst_boruvka", "hdb_exact_mst", "hdb_nearest_sample", "hdb_bubble_stats",
-            "hdb_bubble_partials", "hdb_bubble_combine", "hdb_bubble_core_distances", "hdb_bubble_prim_mst", "hdb_local_model", "hdb_local_model_cores", "hdb_quicksort_edges",
-            "hdb_merge_sorted_runs", "hdb_sort_edges_desc", "hdb_flat_labels", "hdb_flat_outlier_scores", "hdb_flat_cluster_tree",
-            "hdb_cluster_tree_bound", "hdb_labels_at_levels", "hdb_constrained_flat_labels",
-            "hdb_attach_points", "hdb_attach_points_splits", "hdb_predict_labels", "hdb_format_double", "hdb_parse_points",
-            "hdb_format_mst_records", "hdb_parse_mst_records", "hdb_comm_unique_id", "hdb_comm_init",
-            "hdb_comm_destroy", "hdb_free", "hdb_copy", "hdb_merge_edges", "hdb_local_mst_ids"]
 
 
 def check(rc: int, what: str):
     if rc != HDB_OK:
         msg = lib().hdb_last_error().decode(errors="replace")
         raise _EXC.get(rc, HdbError)(rc, f"{what}: {msg}")
+
+
+def call(name: str, *args, what: str | None = None):
+    """One library call that returns a status: raises what check() raises."""
+    check(getattr(lib(), name)(*args), what or name)
 
 
 class Context:
@@ -171,7 +168,7 @@ class Context:
 
     def __init__(self, device: int = 0):
         h = C.c_void_p()
-        check(lib().hdb_ctx_create(device, C.byref(h)), "hdb_ctx_create")
+        call("hdb_ctx_create", device, C.byref(h))
         self.h = h
         self.device = device
         self._stream = None
@@ -192,8 +189,7 @@ class Context:
 
     def set_stream(self, stream_ptr: int | None):
         if stream_ptr != self._stream:
-            check(lib().hdb_ctx_set_stream(self.h, C.c_void_p(stream_ptr) if stream_ptr else None),
-                  "hdb_ctx_set_stream")
+            call("hdb_ctx_set_stream", self.h, C.c_void_p(stream_ptr) if stream_ptr else None)
             self._stream = stream_ptr
 
     def use_torch_stream(self):
@@ -201,25 +197,24 @@ class Context:
         self.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
 
     def set_timing(self, on: bool):
-        check(lib().hdb_ctx_set_timing(self.h, int(on)), "hdb_ctx_set_timing")
+        call("hdb_ctx_set_timing", self.h, int(on))
 
     def kernel_time(self, name: str, reset: bool = True):
         ms = C.c_double()
         n = C.c_int64()
-        check(lib().hdb_ctx_kernel_time(self.h, name.encode(), C.byref(ms), C.byref(n), int(reset)),
-              "hdb_ctx_kernel_time")
+        call("hdb_ctx_kernel_time", self.h, name.encode(), C.byref(ms), C.byref(n), int(reset))
         return ms.value, n.value
 
     def set_option(self, name: str, value: int):
-        check(lib().hdb_ctx_set_option(self.h, name.encode(), int(value)), "hdb_ctx_set_option")
+        call("hdb_ctx_set_option", self.h, name.encode(), int(value))
 
     def get_stat(self, name: str) -> int:
         v = C.c_int64()
-        check(lib().hdb_ctx_get_stat(self.h, name.encode(), C.byref(v)), "hdb_ctx_get_stat")
+        call("hdb_ctx_get_stat", self.h, name.encode(), C.byref(v))
         return v.value
 
     def synchronize(self):
-        check(lib().hdb_ctx_synchronize(self.h), "hdb_ctx_synchronize")
+        call("hdb_ctx_synchronize", self.h)
 
     def __del__(self):
         try:
@@ -262,8 +257,26 @@ class Arr:
         return C.c_void_p(self.ptr)
 
 
+def _on_device(a: Arr) -> bool:
+    return a.device is not None and a.device.type == "cuda"
+
+
+def context_for(ctx, *arrs: Arr, host_ok: bool = False):
+    """The context a call runs on: an explicit ctx as it is; else this thread's context of the
+    first array on a HIP device, on torch's current stream (ordered with the work that made the
+    arrays); with host arrays only, None when the call has a host path (host_ok), else device 0."""
+    if ctx is not None:
+        return ctx
+    for a in arrs:
+        if _on_device(a):
+            c = Context.get(a.device.index or 0)
+            c.use_torch_stream()
+            return c
+    return None if host_ok else Context.get(0)
+
+
 def new_like(ref: Arr, shape, dtype):
-    if ref.device is not None and ref.device.type == "cuda":
+    if _on_device(ref):
         import torch
         tdt = {np.float64: torch.float64, np.int32: torch.int32, np.int64: torch.int64}[dtype]
         return torch.empty(shape, dtype=tdt, device=ref.device)
@@ -276,3 +289,8 @@ def ptr(x):
     if is_torch(x):
         return C.c_void_p(x.data_ptr())
     return C.c_void_p(x.ctypes.data)
+
+
+def new_edges(ref: Arr, ne: int):
+    """Empty (va, vb, w) for ne edges where ref lives."""
+    return new_like(ref, (ne,), np.int32), new_like(ref, (ne,), np.int32), new_like(ref, (ne,), np.float64)

@@ -12,22 +12,6 @@ using namespace hdb;
 
 namespace {
 
-template <class F>
-int guarded(hdb_ctx *ctx, F &&f) {
-    try {
-        if (!ctx) HDB_THROW(HDB_EINVAL, "ctx is NULL");
-        HIP_CHECK(hipSetDevice(ctx->device));
-        f();
-        return HDB_OK;
-    } catch (const Error &e) {
-        set_error(e.msg);
-        return e.code;
-    } catch (const std::bad_alloc &) {
-        set_error("host allocation failed");
-        return HDB_ENOMEM;
-    }
-}
-
 template <class T>
 std::vector<T> to_host(hdb_ctx *ctx, const T *p, size_t count) {
     std::vector<T> v(count);
@@ -45,13 +29,37 @@ void check_metric(int metric) {
     if (metric < HDB_METRIC_EUCLIDEAN || metric > HDB_METRIC_SUPREMUM) HDB_THROW(HDB_EINVAL, "unknown metric");
 }
 
-__global__ void iota_ids_kernel(int32_t *a, int64_t n) { HDB_GRID_STRIDE(i, n) a[i] = (int32_t)i; }
+// The hierarchy entries also run on the host, without a context (all pointers in host memory, no
+// device needed): one argument check, then the part the context selects.
+template <class D, class H>
+int host_or_device(hdb_ctx *ctx, bool bad, D &&device_part, H &&host_part) {
+    const auto check = [&] {
+        if (bad) HDB_THROW(HDB_EINVAL, "bad arguments");
+    };
+    if (!ctx)
+        return entry([&] {
+            check();
+            return host_part();
+        });
+    return guarded(ctx, [&] {
+        check();
+        return device_part();
+    });
+}
 
-const int32_t *identity_ids(hdb_ctx *ctx, int64_t n) {
-    int32_t *ids = (int32_t *)arena(ctx, A_STAGE_OUT, sizeof(int32_t) * std::max<int64_t>(n, 1));
-    hipLaunchKernelGGL(iota_ids_kernel, dim3(1024), dim3(256), 0, ctx->stream, ids, n);
-    HIP_CHECK(hipGetLastError());
-    return ids;
+// CSR offsets of P partitions (host copy, P + 1 values): they start at 0 and never decrease, and
+// with int32_parts no partition has more than INT32_MAX rows.  Returns the edge count: rows - 1
+// tree edges per non-empty partition, plus its rows with self_edges.
+int64_t check_offsets(const std::vector<int64_t> &offs, int P, bool self_edges, bool int32_parts) {
+    if (offs[0] != 0) HDB_THROW(HDB_EINVAL, "offsets[0] must be 0");
+    int64_t ne = 0;
+    for (int p = 0; p < P; p++) {
+        const int64_t np_ = offs[p + 1] - offs[p];
+        if (np_ < 0) HDB_THROW(HDB_EINVAL, "offsets must be non-decreasing");
+        if (int32_parts && np_ > INT32_MAX) HDB_THROW(HDB_EINVAL, "partition too large");
+        if (np_ > 0) ne += (np_ - 1) + (self_edges ? np_ : 0);
+    }
+    return ne;
 }
 
 }  // namespace
@@ -117,15 +125,8 @@ static void prim_common(hdb_ctx *ctx, const double *X, const int64_t *offsets, i
     check_metric(metric);
     if (P < 0 || d <= 0 || !X || !core || !va || !vb || !w) HDB_THROW(HDB_EINVAL, "bad arguments");
     std::vector<int64_t> offs = to_host(ctx, offsets, (size_t)P + 1);
-    if (offs[0] != 0) HDB_THROW(HDB_EINVAL, "offsets[0] must be 0");
-    int64_t n = offs[P];
-    int64_t ne = 0;
-    for (int p = 0; p < P; p++) {
-        int64_t np_ = offs[p + 1] - offs[p];
-        if (np_ < 0) HDB_THROW(HDB_EINVAL, "offsets must be non-decreasing");
-        if (np_ > INT32_MAX) HDB_THROW(HDB_EINVAL, "partition too large");
-        if (np_ > 0) ne += (np_ - 1) + (self_edges ? np_ : 0);
-    }
+    const int64_t ne = check_offsets(offs, P, self_edges != 0, true);
+    const int64_t n = offs[P];
     Stager s(ctx);
     PrimIn in;
     in.X = s.in(X, n * d);
@@ -176,15 +177,12 @@ int hdb_leaf_msts(hdb_ctx *ctx, const double *X, const int64_t *offsets, int32_t
         if (!X || !offsets || !ids || !va || !vb || !w || P < 0 || d <= 0 || min_pts < 1)
             HDB_THROW(HDB_EINVAL, "bad arguments");
         std::vector<int64_t> offs = to_host(ctx, offsets, (size_t)P + 1);
-        if (offs[0] != 0) HDB_THROW(HDB_EINVAL, "offsets[0] must be 0");
+        const int64_t ne = check_offsets(offs, P, true, false);
         const int64_t n = offs[P];
-        int64_t ne = 0;
         std::vector<int32_t> small;
         std::vector<int32_t> large;
         for (int p = 0; p < P; p++) {
-            int64_t np_ = offs[p + 1] - offs[p];
-            if (np_ < 0) HDB_THROW(HDB_EINVAL, "offsets must be non-decreasing");
-            if (np_ > 0) ne += 2 * np_ - 1;
+            const int64_t np_ = offs[p + 1] - offs[p];
             if (np_ > 0 && np_ <= 4096) small.push_back(p);
             else if (np_ > 4096) large.push_back(p);
         }
@@ -403,9 +401,11 @@ int hdb_bubble_prim_mst(hdb_ctx *ctx, const double *rep, const double *eB, const
 
 int hdb_quicksort_edges(int32_t *va, int32_t *vb, double *w, int64_t ne) {
     if (!va || !vb || !w || ne < 0) return HDB_EINVAL;
-    int rc = quicksort_edges(va, vb, w, ne);
-    if (rc) set_error("quicksortByEdgeWeight: stack overflow (ArrayIndexOutOfBoundsException)");
-    return rc;
+    return entry([&] {  // the sort allocates ne-sized host arrays
+        const int rc = quicksort_edges(va, vb, w, ne);
+        if (rc) set_error("quicksortByEdgeWeight: stack overflow (ArrayIndexOutOfBoundsException)");
+        return rc;
+    });
 }
 
 // core_in (nullable, host or device, b values): the bubble core distances already computed by
@@ -492,10 +492,7 @@ int hdb_local_model_cores(hdb_ctx *ctx, const double *rep, const double *info, i
                           int32_t min_pts, int32_t min_cl_size, int32_t metric, const double *core, int32_t *labels,
                           int32_t *mst_va, int32_t *mst_vb, double *mst_w, int32_t *ic_va, int32_t *ic_vb,
                           double *ic_w, int64_t *n_ic) {
-    if (!core) {
-        set_error("hdb_local_model_cores: core is required");
-        return HDB_EINVAL;
-    }
+    if (!core) return entry([] { HDB_THROW(HDB_EINVAL, "hdb_local_model_cores: core is required"); });
     return local_model_impl(ctx, rep, info, b, d, min_pts, min_cl_size, metric, core, labels, mst_va, mst_vb, mst_w,
                             ic_va, ic_vb, ic_w, n_ic);
 }
@@ -547,58 +544,38 @@ int hdb_local_mst_ids(hdb_ctx *ctx, const int32_t *ids, int64_t n, const int32_t
 
 int hdb_flat_labels(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, const double *w, int64_t ne, int64_t n,
                     int32_t min_cl_size, int32_t *labels, int64_t *n_clusters) {
-    if (!ctx) {  // host-only use (all pointers in host memory): no device needed
-        try {
-            if (ne < 0 || n < 0 || (ne > 0 && (!va || !vb || !w)) || (n > 0 && !labels))
-                HDB_THROW(HDB_EINVAL, "bad arguments");
-            return flat_labels_host(va, vb, w, ne, n, min_cl_size, labels, n_clusters);
-        } catch (const Error &e) {
-            set_error(e.msg);
-            return e.code;
-        } catch (const std::bad_alloc &) {
-            set_error("host allocation failed");
-            return HDB_ENOMEM;
-        }
-    }
-    return guarded(ctx, [&] {
-        if (ne < 0 || n < 0 || (ne > 0 && (!va || !vb || !w)) || (n > 0 && !labels)) HDB_THROW(HDB_EINVAL, "bad arguments");
-        // device algorithm (K6, flat.hip); host arrays are staged
-        Stager sg(ctx);
-        const int32_t *da = sg.in(va, (size_t)ne), *db = sg.in(vb, (size_t)ne);
-        const double *dw = sg.in(w, (size_t)ne);
-        int32_t *dl = sg.out(labels, (size_t)std::max<int64_t>(n, 0));
-        flat_labels_device(ctx, da, db, dw, ne, n, min_cl_size, dl, n_clusters);
-        sg.finish();
-    });
+    const bool bad = ne < 0 || n < 0 || (ne > 0 && (!va || !vb || !w)) || (n > 0 && !labels);
+    return host_or_device(
+        ctx, bad,
+        [&] {
+            // device algorithm (K6, flat.hip); host arrays are staged
+            Stager sg(ctx);
+            const int32_t *da = sg.in(va, (size_t)ne), *db = sg.in(vb, (size_t)ne);
+            const double *dw = sg.in(w, (size_t)ne);
+            int32_t *dl = sg.out(labels, (size_t)std::max<int64_t>(n, 0));
+            flat_labels_device(ctx, da, db, dw, ne, n, min_cl_size, dl, n_clusters);
+            sg.finish();
+        },
+        [&] { return flat_labels_host(va, vb, w, ne, n, min_cl_size, labels, n_clusters); });
 }
 
 int hdb_flat_outlier_scores(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, const double *w, int64_t ne, int64_t n,
                             int32_t min_cl_size, double *scores, double *noise_level, int32_t *labels,
                             int64_t *n_clusters) {
-    if (!ctx) {  // host-only use (all pointers in host memory): no device needed
-        try {
-            if (ne < 0 || n < 0 || (ne > 0 && (!va || !vb || !w)) || (n > 0 && !scores))
-                HDB_THROW(HDB_EINVAL, "bad arguments");
-            return flat_outlier_scores_host(va, vb, w, ne, n, min_cl_size, scores, noise_level, labels, n_clusters);
-        } catch (const Error &e) {
-            set_error(e.msg);
-            return e.code;
-        } catch (const std::bad_alloc &) {
-            set_error("host allocation failed");
-            return HDB_ENOMEM;
-        }
-    }
-    return guarded(ctx, [&] {
-        if (ne < 0 || n < 0 || (ne > 0 && (!va || !vb || !w)) || (n > 0 && !scores)) HDB_THROW(HDB_EINVAL, "bad arguments");
-        Stager sg(ctx);
-        const int32_t *da = sg.in(va, (size_t)ne), *db = sg.in(vb, (size_t)ne);
-        const double *dw = sg.in(w, (size_t)ne);
-        const size_t np = (size_t)std::max<int64_t>(n, 0);
-        double *ds = sg.out(scores, np), *dn = sg.out(noise_level, np);
-        int32_t *dl = sg.out(labels, np);
-        flat_outlier_scores_device(ctx, da, db, dw, ne, n, min_cl_size, ds, dn, dl, n_clusters);
-        sg.finish();
-    });
+    const bool bad = ne < 0 || n < 0 || (ne > 0 && (!va || !vb || !w)) || (n > 0 && !scores);
+    return host_or_device(
+        ctx, bad,
+        [&] {
+            Stager sg(ctx);
+            const int32_t *da = sg.in(va, (size_t)ne), *db = sg.in(vb, (size_t)ne);
+            const double *dw = sg.in(w, (size_t)ne);
+            const size_t np = (size_t)std::max<int64_t>(n, 0);
+            double *ds = sg.out(scores, np), *dn = sg.out(noise_level, np);
+            int32_t *dl = sg.out(labels, np);
+            flat_outlier_scores_device(ctx, da, db, dw, ne, n, min_cl_size, ds, dn, dl, n_clusters);
+            sg.finish();
+        },
+        [&] { return flat_outlier_scores_host(va, vb, w, ne, n, min_cl_size, scores, noise_level, labels, n_clusters); });
 }
 
 int64_t hdb_cluster_tree_bound(int64_t n, int32_t min_cl_size) { return cluster_tree_bound(n, min_cl_size); }
@@ -608,34 +585,26 @@ int hdb_flat_cluster_tree(hdb_ctx *ctx, const int32_t *va, const int32_t *vb, co
                           double *birth, double *death, double *stability, int32_t *size, int32_t *min_id,
                           int32_t *flat_label, int32_t *point_cluster, double *point_level, int64_t *n_clusters) {
     const bool bad = ne < 0 || n < 0 || cap < 0 || !n_tree || (ne > 0 && (!va || !vb || !w));
-    if (!ctx) {  // host-only use (all pointers in host memory): no device needed
-        try {
-            if (bad) HDB_THROW(HDB_EINVAL, "bad arguments");
+    return host_or_device(
+        ctx, bad,
+        [&] {
+            Stager sg(ctx);
+            const int32_t *da = sg.in(va, (size_t)ne), *db = sg.in(vb, (size_t)ne);
+            const double *dw = sg.in(w, (size_t)ne);
+            // staged per-cluster outputs are sized by what the tree can hold, not by a generous cap
+            const size_t nk = (size_t)std::min<int64_t>(cap, cluster_tree_bound(n, std::max<int32_t>(min_cl_size, 2)));
+            const size_t np = (size_t)n;
+            ClusterTreeOut t{(int64_t)nk, n_tree, sg.out(parent, nk), sg.out(birth, nk), sg.out(death, nk),
+                             sg.out(stability, nk), sg.out(size, nk), sg.out(min_id, nk), sg.out(flat_label, nk),
+                             sg.out(point_cluster, np), sg.out(point_level, np)};
+            flat_cluster_tree_device(ctx, da, db, dw, ne, n, min_cl_size, t, n_clusters);
+            sg.finish();
+        },
+        [&] {
             const ClusterTreeOut t{cap, n_tree, parent, birth, death, stability, size, min_id, flat_label,
                                    point_cluster, point_level};
             return flat_cluster_tree_host(va, vb, w, ne, n, min_cl_size, t, nullptr, n_clusters);
-        } catch (const Error &e) {
-            set_error(e.msg);
-            return e.code;
-        } catch (const std::bad_alloc &) {
-            set_error("host allocation failed");
-            return HDB_ENOMEM;
-        }
-    }
-    return guarded(ctx, [&] {
-        if (bad) HDB_THROW(HDB_EINVAL, "bad arguments");
-        Stager sg(ctx);
-        const int32_t *da = sg.in(va, (size_t)ne), *db = sg.in(vb, (size_t)ne);
-        const double *dw = sg.in(w, (size_t)ne);
-        // staged per-cluster outputs are sized by what the tree can hold, not by a generous cap
-        const size_t nk = (size_t)std::min<int64_t>(cap, cluster_tree_bound(n, std::max<int32_t>(min_cl_size, 2)));
-        const size_t np = (size_t)n;
-        ClusterTreeOut t{(int64_t)nk, n_tree, sg.out(parent, nk), sg.out(birth, nk), sg.out(death, nk),
-                         sg.out(stability, nk), sg.out(size, nk), sg.out(min_id, nk), sg.out(flat_label, nk),
-                         sg.out(point_cluster, np), sg.out(point_level, np)};
-        flat_cluster_tree_device(ctx, da, db, dw, ne, n, min_cl_size, t, n_clusters);
-        sg.finish();
-    });
+        });
 }
 
 int hdb_labels_at_levels(hdb_ctx *ctx, const int32_t *parent, const double *birth, int64_t K,
@@ -643,28 +612,18 @@ int hdb_labels_at_levels(hdb_ctx *ctx, const int32_t *parent, const double *birt
                          const double *levels, int32_t L, int32_t *labels_out) {
     const bool bad = K < 0 || n < 0 || L < 0 || (L > 0 && !levels) || (K > 0 && (!parent || !birth)) ||
                      (n > 0 && (!point_cluster || !point_level)) || (n > 0 && L > 0 && !labels_out);
-    if (!ctx) {  // host-only use (all pointers in host memory): no device needed
-        try {
-            if (bad) HDB_THROW(HDB_EINVAL, "bad arguments");
-            return labels_at_levels_host(parent, birth, K, point_cluster, point_level, n, levels, L, labels_out);
-        } catch (const Error &e) {
-            set_error(e.msg);
-            return e.code;
-        } catch (const std::bad_alloc &) {
-            set_error("host allocation failed");
-            return HDB_ENOMEM;
-        }
-    }
-    return guarded(ctx, [&] {
-        if (bad) HDB_THROW(HDB_EINVAL, "bad arguments");
-        Stager sg(ctx);
-        const int32_t *dp = sg.in(parent, (size_t)K), *dpc = sg.in(point_cluster, (size_t)n);
-        const double *db = sg.in(birth, (size_t)K), *dpl = sg.in(point_level, (size_t)n);
-        const double *dlv = sg.in(levels, (size_t)L);
-        int32_t *dout = sg.out(labels_out, (size_t)L * (size_t)n);
-        labels_at_levels_device(ctx, dp, db, K, dpc, dpl, n, dlv, L, dout);
-        sg.finish();
-    });
+    return host_or_device(
+        ctx, bad,
+        [&] {
+            Stager sg(ctx);
+            const int32_t *dp = sg.in(parent, (size_t)K), *dpc = sg.in(point_cluster, (size_t)n);
+            const double *db = sg.in(birth, (size_t)K), *dpl = sg.in(point_level, (size_t)n);
+            const double *dlv = sg.in(levels, (size_t)L);
+            int32_t *dout = sg.out(labels_out, (size_t)L * (size_t)n);
+            labels_at_levels_device(ctx, dp, db, K, dpc, dpl, n, dlv, L, dout);
+            sg.finish();
+        },
+        [&] { return labels_at_levels_host(parent, birth, K, point_cluster, point_level, n, levels, L, labels_out); });
 }
 
 int hdb_predict_labels(hdb_ctx *ctx, const int32_t *parent, const double *birth, const double *death,
@@ -673,33 +632,25 @@ int hdb_predict_labels(hdb_ctx *ctx, const int32_t *parent, const double *birth,
                        int64_t m, int32_t *tree_label, int32_t *labels, double *scores) {
     const bool bad = K < 0 || n < 0 || m < 0 || (K > 0 && (!parent || !birth || !death || !flat_label)) ||
                      (n > 0 && (!point_cluster || !point_level)) || (m > 0 && (!nearest || !level));
-    if (!ctx) {  // host-only use (all pointers in host memory): no device needed
-        try {
-            if (bad) HDB_THROW(HDB_EINVAL, "bad arguments");
+    return host_or_device(
+        ctx, bad,
+        [&] {
+            if (m == 0) return;
+            Stager sg(ctx);
+            const size_t nk = (size_t)K, np = (size_t)n, nm = (size_t)m;
+            const int32_t *dp = sg.in(parent, nk), *dfl = sg.in(flat_label, nk), *dpc = sg.in(point_cluster, np);
+            const double *db = sg.in(birth, nk), *dd = sg.in(death, nk), *dpl = sg.in(point_level, np);
+            const int32_t *dnr = sg.in(nearest, nm);
+            const double *dlv = sg.in(level, nm);
+            int32_t *dtl = sg.out(tree_label, nm), *dlab = sg.out(labels, nm);
+            double *dsc = sg.out(scores, nm);
+            predict_labels_device(ctx, dp, db, dd, dfl, K, dpc, dpl, n, dnr, dlv, m, dtl, dlab, dsc);
+            sg.finish();
+        },
+        [&] {
             return predict_labels_host(parent, birth, death, flat_label, K, point_cluster, point_level, n, nearest,
                                        level, m, tree_label, labels, scores);
-        } catch (const Error &e) {
-            set_error(e.msg);
-            return e.code;
-        } catch (const std::bad_alloc &) {
-            set_error("host allocation failed");
-            return HDB_ENOMEM;
-        }
-    }
-    return guarded(ctx, [&] {
-        if (bad) HDB_THROW(HDB_EINVAL, "bad arguments");
-        if (m == 0) return;
-        Stager sg(ctx);
-        const size_t nk = (size_t)K, np = (size_t)n, nm = (size_t)m;
-        const int32_t *dp = sg.in(parent, nk), *dfl = sg.in(flat_label, nk), *dpc = sg.in(point_cluster, np);
-        const double *db = sg.in(birth, nk), *dd = sg.in(death, nk), *dpl = sg.in(point_level, np);
-        const int32_t *dnr = sg.in(nearest, nm);
-        const double *dlv = sg.in(level, nm);
-        int32_t *dtl = sg.out(tree_label, nm), *dlab = sg.out(labels, nm);
-        double *dsc = sg.out(scores, nm);
-        predict_labels_device(ctx, dp, db, dd, dfl, K, dpc, dpl, n, dnr, dlv, m, dtl, dlab, dsc);
-        sg.finish();
-    });
+        });
 }
 
 int hdb_constrained_flat_labels(hdb_ctx *ctx, const int32_t *parent, const double *stability, const int32_t *min_id,
@@ -707,27 +658,17 @@ int hdb_constrained_flat_labels(hdb_ctx *ctx, const int32_t *parent, const doubl
                                 const int32_t *cb, const int32_t *ctype, int64_t m, int32_t *num_sat,
                                 int32_t *prop_sat, double *prop_stability, int32_t *flat_label, int32_t *labels,
                                 int64_t *n_clusters) {
-    // the host path makes these checks itself; here they come before any array is staged
-    auto precheck = [&] {
+    if (!ctx)  // the host path makes its own checks
+        return entry([&] {
+            const ConstrainedOut o{num_sat, prop_sat, prop_stability, flat_label, labels, n_clusters};
+            return constrained_flat_labels_host(parent, stability, min_id, K, point_cluster, n, ca, cb, ctype, m, o);
+        });
+    return guarded(ctx, [&] {
+        // the same checks, here before any array is staged
         if (m > HDB_MAX_CONSTRAINTS) HDB_THROW(HDB_EINVAL, "constrained flat labels: m exceeds 2^30 - 1 constraints");
         if (K < 0 || n < 0 || m < 0 || (K > 0 && (!parent || !stability || !min_id)) || (n > 0 && !point_cluster) ||
             (m > 0 && (!ca || !cb || !ctype)))
             HDB_THROW(HDB_EINVAL, "bad arguments");
-    };
-    if (!ctx) {  // host-only use (all pointers in host memory): no device needed
-        try {
-            const ConstrainedOut o{num_sat, prop_sat, prop_stability, flat_label, labels, n_clusters};
-            return constrained_flat_labels_host(parent, stability, min_id, K, point_cluster, n, ca, cb, ctype, m, o);
-        } catch (const Error &e) {
-            set_error(e.msg);
-            return e.code;
-        } catch (const std::bad_alloc &) {
-            set_error("host allocation failed");
-            return HDB_ENOMEM;
-        }
-    }
-    return guarded(ctx, [&] {
-        precheck();
         Stager sg(ctx);
         const size_t nk = (size_t)K, np = (size_t)n, nm = (size_t)m;
         const int32_t *dp = sg.in(parent, nk), *dmin = sg.in(min_id, nk), *dpc = sg.in(point_cluster, np);

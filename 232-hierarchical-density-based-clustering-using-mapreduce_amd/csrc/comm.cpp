@@ -101,20 +101,17 @@ using namespace hdb;
 extern "C" {
 
 int hdb_comm_unique_id(void *id_out, int32_t cap) {
-    try {
+    return entry([&] {
         if (!id_out || cap < (int32_t)sizeof(ncclUniqueId)) HDB_THROW(HDB_EINVAL, "id buffer too small");
         ncclUniqueId id;
         RCCL_CHECK(rccl().get_unique_id(&id));
         std::memcpy(id_out, &id, sizeof(id));
         return (int)sizeof(id);
-    } catch (const Error &e) {
-        set_error(e.msg);
-        return e.code;
-    }
+    });
 }
 
 int hdb_comm_init(hdb_ctx *ctx, int32_t nranks, int32_t rank, const void *id, hdb_comm **out) {
-    try {
+    return entry([&] {
         if (!ctx || !id || !out || nranks < 1 || rank < 0 || rank >= nranks) HDB_THROW(HDB_EINVAL, "bad arguments");
         HIP_CHECK(hipSetDevice(ctx->device));
         ncclUniqueId uid;
@@ -129,18 +126,14 @@ int hdb_comm_init(hdb_ctx *ctx, int32_t nranks, int32_t rank, const void *id, hd
             RCCL_CHECK(r);
         }
         *out = c;
-        return HDB_OK;
-    } catch (const Error &e) {
-        set_error(e.msg);
-        return e.code;
-    }
+    });
 }
 
 void hdb_comm_destroy(hdb_comm *comm) {
     if (!comm) return;
     try {
         if (comm->comm) rccl().comm_destroy(comm->comm);
-    } catch (const Error &) {
+    } catch (...) {  // a destroy reports nothing
     }
     delete comm;
 }
@@ -152,24 +145,17 @@ int hdb_free(void *p) {
 
 int hdb_copy(hdb_ctx *ctx, void *dst, const void *src, int64_t bytes) {
     if (!ctx || bytes < 0 || (bytes && (!dst || !src))) return HDB_EINVAL;
-    try {
+    return entry([&] {
         HIP_CHECK(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDefault, ctx->stream));
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        return HDB_OK;
-    } catch (const Error &e) {
-        set_error(e.msg);
-        return e.code;
-    }
+    });
 }
 
 int hdb_merge_edges(hdb_comm *comm, const int32_t *va, const int32_t *vb, const double *w, const int64_t *seq,
                     int64_t e_local, int32_t **va_all, int32_t **vb_all, double **w_all, int64_t *e_all) {
-    if (!comm || !comm->ctx) {
-        set_error("comm is NULL");
-        return HDB_EINVAL;
-    }
+    if (!comm || !comm->ctx) return entry([] { HDB_THROW(HDB_EINVAL, "comm is NULL"); });
     hdb_ctx *ctx = comm->ctx;
-    try {
+    return entry([&] {
         if (e_local < 0 || !va_all || !vb_all || !w_all || !e_all || (e_local > 0 && (!va || !vb || !w)))
             HDB_THROW(HDB_EINVAL, "bad arguments");
         HIP_CHECK(hipSetDevice(ctx->device));
@@ -275,14 +261,7 @@ int hdb_merge_edges(hdb_comm *comm, const int32_t *va, const int32_t *vb, const 
         *vb_all = ob;
         *w_all = ow;
         *e_all = E;
-        return HDB_OK;
-    } catch (const Error &e) {
-        set_error(e.msg);
-        return e.code;
-    } catch (const std::bad_alloc &) {
-        set_error("host allocation failed");
-        return HDB_ENOMEM;
-    }
+    });
 }
 
 }  // extern "C"

@@ -20,6 +20,7 @@ constexpr double JMAX = DBL_MAX;  // Double.MAX_VALUE
 
 // ----------------------------------------------------------------- errors
 void set_error(const std::string &msg);
+const char *last_error();
 struct Error {
     int code;
     std::string msg;
@@ -123,6 +124,8 @@ enum {
 };
 
 void *arena(hdb_ctx *ctx, int slot, size_t bytes);
+// HDB_OPTS: "name=value,..." applied pair by pair with hdb_ctx_set_option (options.cpp)
+int apply_opts(hdb_ctx *ctx, const char *opts);
 
 // Device scratch layout.  Every arena is handed out by one bump carver, and every layout is written once,
 // as a function of a Carver: carve() runs it on a null base to size the arena, then on the real base to

@@ -1,10 +1,10 @@
-// context.cpp -- hdb_ctx lifetime, scratch arenas, kernel timing, host/device staging.
+// context.cpp -- hdb_ctx lifetime, scratch arenas, kernel timing, host/device staging
+// (runtime options: options.cpp).
 #include <execinfo.h>
 #include <signal.h>
 #include <unistd.h>
 
 #include <algorithm>
-#include <cerrno>
 #include <cstdlib>
 
 #include "common.hpp"
@@ -217,41 +217,13 @@ void Stager::finish() {
 
 using namespace hdb;
 
-// "name=value,name=value" through hdb_ctx_set_option; the first pair that is malformed or
-// rejected ends it with that status and names the pair in last_error()
-static int apply_opts(hdb_ctx *c, const char *opts) {
-    const std::string s(opts);
-    for (size_t a = 0; a < s.size();) {
-        const size_t b = std::min(s.find(',', a), s.size());
-        const std::string pair = s.substr(a, b - a);
-        a = b + 1;
-        if (pair.empty()) continue;
-        const size_t eq = pair.find('=');
-        char *end = nullptr;
-        errno = 0;
-        const long long v = eq == std::string::npos ? 0 : strtoll(pair.c_str() + eq + 1, &end, 10);
-        if (eq == std::string::npos || eq == 0 || end == pair.c_str() + eq + 1 || *end != '\0' || errno == ERANGE) {
-            set_error("malformed pair '" + pair + "' (name=integer)");
-            return HDB_EINVAL;
-        }
-        set_error("");
-        const int rc = hdb_ctx_set_option(c, pair.substr(0, eq).c_str(), (int64_t)v);
-        if (rc != HDB_OK) {
-            const std::string why = last_error();
-            set_error("'" + pair + "' rejected" + (why.empty() ? std::string(" (value out of range)") : ": " + why));
-            return rc;
-        }
-    }
-    return HDB_OK;
-}
-
 extern "C" {
 
 const char *hdb_last_error(void) { return hdb::last_error(); }
 int hdb_version(void) { return 100; }
 
 int hdb_ctx_create(int device, hdb_ctx **out) {
-    try {
+    return entry([&] {
         if (!out) HDB_THROW(HDB_EINVAL, "out is NULL");
         int count = 0;
         HIP_CHECK(hipGetDeviceCount(&count));
@@ -283,11 +255,7 @@ int hdb_ctx_create(int device, hdb_ctx **out) {
             }
         }
         *out = c;
-        return HDB_OK;
-    } catch (const Error &e) {
-        set_error(e.msg);
-        return e.code;
-    }
+    });
 }
 
 void hdb_ctx_destroy(hdb_ctx *ctx) {
@@ -314,9 +282,7 @@ void hdb_ctx_destroy(hdb_ctx *ctx) {
 }
 
 int hdb_ctx_set_stream(hdb_ctx *ctx, void *stream) {
-    try {
-        if (!ctx) HDB_THROW(HDB_EINVAL, "ctx is NULL");
-        HIP_CHECK(hipSetDevice(ctx->device));
+    return guarded(ctx, [&] {
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
         if (ctx->own_stream) HIP_CHECK(hipStreamDestroy(ctx->stream));
         // NULL selects the device's default (null) stream -- what PyTorch reports as
@@ -324,11 +290,7 @@ int hdb_ctx_set_stream(hdb_ctx *ctx, void *stream) {
         // ordered with the caller's.
         ctx->stream = (hipStream_t)stream;
         ctx->own_stream = false;
-        return HDB_OK;
-    } catch (const Error &e) {
-        set_error(e.msg);
-        return e.code;
-    }
+    });
 }
 
 int hdb_ctx_set_timing(hdb_ctx *ctx, int enable) {
@@ -338,7 +300,7 @@ int hdb_ctx_set_timing(hdb_ctx *ctx, int enable) {
 }
 
 int hdb_ctx_kernel_time(hdb_ctx *ctx, const char *name, double *ms_total, int64_t *launches, int reset) {
-    try {
+    return entry([&] {
         if (!ctx || !name) HDB_THROW(HDB_EINVAL, "NULL argument");
         HIP_CHECK(hipSetDevice(ctx->device));
         drain_timing(ctx);
@@ -352,197 +314,23 @@ int hdb_ctx_kernel_time(hdb_ctx *ctx, const char *name, double *ms_total, int64_
         }
         if (ms_total) *ms_total = ms;
         if (launches) *launches = n;
-        return HDB_OK;
-    } catch (const Error &e) {
-        set_error(e.msg);
-        return e.code;
-    }
-}
-
-int hdb_ctx_set_option(hdb_ctx *ctx, const char *name, int64_t value) {
-    if (!ctx || !name) return HDB_EINVAL;
-    const std::string k(name);
-    if (k == "knn_fp32_screen") {
-        ctx->force_fp64 = value == 0;
-        return HDB_OK;
-    }
-    if (k == "knn_tree") {
-        ctx->knn_tree = value != 0;
-        return HDB_OK;
-    }
-    if (k == "knn_mfma") {
-        ctx->knn_mfma = value != 0;
-        return HDB_OK;
-    }
-    if (k == "nearest_grouped") {
-        ctx->nearest_grouped = value != 0;
-        return HDB_OK;
-    }
-    if (k == "knn_mfma_prune") {
-        ctx->knn_mfma_prune = value != 0;
-        return HDB_OK;
-    }
-    if (k == "knn_mfma_single") {
-        ctx->knn_mfma_single = value != 0;
-        return HDB_OK;
-    }
-    if (k == "knn_mfma_min_n") {
-        ctx->knn_mfma_min_n = value;
-        return HDB_OK;
-    }
-    if (k == "knn_tree_min_n") {
-        ctx->knn_tree_min_n = value;
-        return HDB_OK;
-    }
-    if (k == "prim_coop_plain") {
-        ctx->prim_coop_plain = value != 0;
-        return HDB_OK;
-    }
-    if (k == "bubble_fold_dim") {
-        ctx->bubble_fold_dim = value != 0;
-        return HDB_OK;
-    }
-    if (k == "bubble_knn_split") {
-        ctx->bubble_knn_split = value != 0;
-        return HDB_OK;
-    }
-    if (k == "prim_coop_xcd") {
-        ctx->prim_coop_xcd = value != 0;
-        return HDB_OK;
-    }
-    if (k == "prim_coop_plain_spin_log2") {
-        if (value < 0 || value > 24) return HDB_EINVAL;
-        ctx->prim_coop_plain_spin_log2 = (int)value;
-        return HDB_OK;
-    }
-    if (k == "prim_coop") {
-        ctx->prim_coop = value != 0;
-        return HDB_OK;
-    }
-    if (k == "prim_coop_bs") {
-        if (value != 0 && value != 128 && value != 256 && value != 512 && value != 1024) return HDB_EINVAL;
-        ctx->prim_coop_bs = (int)value;
-        return HDB_OK;
-    }
-    if (k == "prim_coop_slots") {
-        if (value != 4 && value != 0) return HDB_EINVAL;
-        ctx->prim_coop_slots = (int)value;
-        return HDB_OK;
-    }
-    if (k == "leaf_seed_k") {
-        if (value < -1 || value > 31) return HDB_EINVAL;
-        ctx->leaf_seed_k = (int)value;
-        return HDB_OK;
-    }
-    if (k == "leaf_list_rounds") {
-        if (value < 0) return HDB_EINVAL;
-        ctx->leaf_list_rounds = (int)value;
-        return HDB_OK;
-    }
-    if (k == "boruvka_seed") {
-        ctx->boruvka_seed = value != 0;
-        return HDB_OK;
-    }
-    if (k == "trav_pop_test") {
-        ctx->trav_pop_test = (int)value;
-        return HDB_OK;
-    }
-    if (k == "bor_xcd_chunks") {
-        if (value < 0 || value > 4096) return HDB_EINVAL;
-        ctx->bor_xcd_chunks = (int)value;
-        return HDB_OK;
-    }
-    if (k == "k1t_xcd_chunks") {
-        if (value < 0 || value > 4096) return HDB_EINVAL;
-        ctx->k1t_xcd_chunks = (int)value;
-        return HDB_OK;
-    }
-    if (k == "boruvka_adj_seed") {
-        ctx->boruvka_adj_seed = value != 0;
-        return HDB_OK;
-    }
-    if (k == "boruvka_wave_pts") {
-        ctx->boruvka_wave_pts = (int)value;
-        return HDB_OK;
-    }
-    if (k == "boruvka_early_pts") {
-        ctx->boruvka_early_pts = (int)value;
-        return HDB_OK;
-    }
-    if (k == "boruvka_early_rounds") {
-        ctx->boruvka_early_rounds = (int)value;
-        return HDB_OK;
-    }
-    if (k == "boruvka_knn_seed") {
-        ctx->boruvka_knn_seed = value != 0;
-        return HDB_OK;
-    }
-    if (k == "flat_mid_log") {
-        if (value < 0 || value > 24) return HDB_EINVAL;
-        ctx->flat_mid_log = (int)value;
-        return HDB_OK;
-    }
-    if (k == "flat_block_log") {
-        if (value != 0 && (value < 8 || value > 10)) return HDB_EINVAL;
-        ctx->flat_block_log = (int)value;
-        return HDB_OK;
-    }
-    if (k == "flat_root_variant" || k == "flat_deep_root") {
-        if (value < 0 || value > 5) return HDB_EINVAL;
-        (k == "flat_root_variant" ? ctx->flat_root_variant : ctx->flat_deep_root) = (int)value;
-        return HDB_OK;
-    }
-    if (k == "flat_link_variant" || k == "flat_deep_link") {
-        if (value < 0 || value > 1) return HDB_EINVAL;
-        (k == "flat_link_variant" ? ctx->flat_link_variant : ctx->flat_deep_link) = (int)value;
-        return HDB_OK;
-    }
-    if (k == "flat_deep_depth") {
-        if (value < 0 || value > 64) return HDB_EINVAL;
-        ctx->flat_deep_depth = (int)value;
-        return HDB_OK;
-    }
-    if (k == "flat_relabel") {
-        ctx->flat_relabel = value != 0;
-        return HDB_OK;
-    }
-    if (k == "ssort") {
-        ctx->ssort = value != 0;
-        return HDB_OK;
-    }
-    if (k == "ssort_cap") {
-        if (value < 0 || value > 4096) return HDB_EINVAL;
-        ctx->ssort_cap = (int)value;
-        return HDB_OK;
-    }
-    if (k == "count_evals") {
-        ctx->count_evals = value != 0;
-        return HDB_OK;
-    }
-    set_error(std::string("unknown option ") + name);
-    return HDB_EINVAL;
+    });
 }
 
 int hdb_ctx_get_stat(hdb_ctx *ctx, const char *name, int64_t *value) {
     if (!ctx || !name || !value) return HDB_EINVAL;
-    auto it = ctx->stats.find(name);
-    if (it != ctx->stats.end()) {
+    return entry([&] {
+        auto it = ctx->stats.find(name);
+        if (it == ctx->stats.end()) HDB_THROW(HDB_EINVAL, std::string("unknown stat ") + name);
         *value = it->second;
-        return HDB_OK;
-    }
-    set_error(std::string("unknown stat ") + name);
-    return HDB_EINVAL;
+    });
 }
 
 int hdb_ctx_synchronize(hdb_ctx *ctx) {
-    try {
+    return entry([&] {  // no device selection: the stream carries its device
         if (!ctx) HDB_THROW(HDB_EINVAL, "ctx is NULL");
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        return HDB_OK;
-    } catch (const Error &e) {
-        set_error(e.msg);
-        return e.code;
-    }
+    });
 }
 
 }  // extern "C"

@@ -1,10 +1,41 @@
 // internal.hpp -- device-side building blocks shared by the C-ABI layer.
 #pragma once
 #include <algorithm>
+#include <new>
+#include <type_traits>
 
 #include "common.hpp"
 
 namespace hdb {
+
+// The guard of the C ABI: every extern "C" function that can throw runs its body through entry()
+// or guarded(), so no exception leaves the library.  f returns a status, or nothing for HDB_OK.
+template <class F>
+int entry(F &&f) {
+    try {
+        if constexpr (std::is_void_v<decltype(f())>) {
+            f();
+            return HDB_OK;
+        } else {
+            return f();
+        }
+    } catch (const Error &e) {
+        set_error(e.msg);
+        return e.code;
+    } catch (const std::bad_alloc &) {
+        set_error("host allocation failed");
+        return HDB_ENOMEM;
+    }
+}
+// entry() for a call that runs on ctx's device
+template <class F>
+int guarded(hdb_ctx *ctx, F &&f) {
+    return entry([&] {
+        if (!ctx) HDB_THROW(HDB_EINVAL, "ctx is NULL");
+        HIP_CHECK(hipSetDevice(ctx->device));
+        return f();
+    });
+}
 
 struct PrimIn {
     const double *X;

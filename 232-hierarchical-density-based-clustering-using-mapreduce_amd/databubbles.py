@@ -7,7 +7,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _capi as A
-from .hdbscanstar import UndirectedGraph, _ctx, metric_of
+from .hdbscanstar import UndirectedGraph, metric_of
 
 
 class HdbscanDataBubbles:
@@ -25,9 +25,9 @@ class HdbscanDataBubbles:
         b, d = R.obj.shape
         nb_, e, nn = A.Arr(nB, np.int32), A.Arr(eB, np.float64), A.Arr(nnDistB, np.float64)
         core = A.new_like(R, (b,), np.float64)
-        c = _ctx(R, self.ctx)
-        A.check(A.lib().hdb_bubble_core_distances(c.h, R.p, nb_.p, e.p, nn.p, b, d, k, metric_of(distanceFunction),
-                                                  A.ptr(core)), "calculateCoreDistancesBubbles")
+        c = A.context_for(self.ctx, R)
+        A.call("hdb_bubble_core_distances", c.h, R.p, nb_.p, e.p, nn.p, b, d, k, metric_of(distanceFunction),
+               A.ptr(core), what="calculateCoreDistancesBubbles")
         return core
 
     def constructMSTBubbles(self, dataRepB, nB, eB, nnDistB, idBubbles, coreDistances, selfEdges: bool,
@@ -39,13 +39,10 @@ class HdbscanDataBubbles:
         ids = A.Arr(idBubbles, np.int32)
         core = A.Arr(coreDistances, np.float64)
         ne = (b - 1) + (b if selfEdges else 0)
-        va = A.new_like(R, (ne,), np.int32)
-        vb = A.new_like(R, (ne,), np.int32)
-        w = A.new_like(R, (ne,), np.float64)
-        c = _ctx(R, self.ctx)
-        A.check(A.lib().hdb_bubble_prim_mst(c.h, R.p, e.p, nn.p, ids.p, core.p, b, d, metric_of(distanceFunction),
-                                            int(bool(selfEdges)), A.ptr(va), A.ptr(vb), A.ptr(w)),
-                "constructMSTBubbles")
+        va, vb, w = A.new_edges(R, ne)
+        c = A.context_for(self.ctx, R)
+        A.call("hdb_bubble_prim_mst", c.h, R.p, e.p, nn.p, ids.p, core.p, b, d, metric_of(distanceFunction),
+               int(bool(selfEdges)), A.ptr(va), A.ptr(vb), A.ptr(w), what="constructMSTBubbles")
         return UndirectedGraph(va, vb, w, b)
 
     def localModel(self, rep, info, minPts: int, minClSize: int, distanceFunction=None):
@@ -58,10 +55,10 @@ class HdbscanDataBubbles:
         mva, mvb, mw = np.zeros(ne, np.int32), np.zeros(ne, np.int32), np.zeros(ne)
         iva, ivb, iw = np.zeros(ne, np.int32), np.zeros(ne, np.int32), np.zeros(ne)
         nic = np.zeros(1, np.int64)
-        c = self.ctx or A.Context.get(0)
-        A.check(A.lib().hdb_local_model(c.h, A.ptr(R), A.ptr(I), b, d, minPts, minClSize,
-                                        metric_of(distanceFunction), A.ptr(labels), A.ptr(mva), A.ptr(mvb),
-                                        A.ptr(mw), A.ptr(iva), A.ptr(ivb), A.ptr(iw), A.ptr(nic)), "localModel")
+        c = A.context_for(self.ctx)
+        A.call("hdb_local_model", c.h, A.ptr(R), A.ptr(I), b, d, minPts, minClSize, metric_of(distanceFunction),
+               A.ptr(labels), A.ptr(mva), A.ptr(mvb), A.ptr(mw), A.ptr(iva), A.ptr(ivb), A.ptr(iw), A.ptr(nic),
+               what="localModel")
         k = int(nic[0])
         self.vertice1, self.vertice2, self.dmreach = (iva[:k], ivb[:k], iw[:k]) if k else (None, None, None)
         return labels, UndirectedGraph(mva, mvb, mw, b), (iva[:k], ivb[:k], iw[:k])
@@ -93,10 +90,9 @@ def nearest_sample(X, S, distanceFunction=None, x_key=None, s_key=None, ctx=None
     dist = A.new_like(XX, (n,), np.float64) if with_dist else None
     xk = A.Arr(x_key, np.int32) if x_key is not None else None
     sk = A.Arr(s_key, np.int32) if s_key is not None else None
-    c = _ctx(XX, ctx)
-    A.check(A.lib().hdb_nearest_sample(c.h, XX.p, n, SS.p, m, d, metric_of(distanceFunction),
-                                       xk.p if xk else None, sk.p if sk else None, A.ptr(out), A.ptr(dist)),
-            "nearest_sample")
+    c = A.context_for(ctx, XX)
+    A.call("hdb_nearest_sample", c.h, XX.p, n, SS.p, m, d, metric_of(distanceFunction), xk.p if xk else None,
+           sk.p if sk else None, A.ptr(out), A.ptr(dist), what="nearest_sample")
     return (out, dist) if with_dist else out
 
 
@@ -110,9 +106,9 @@ def bubble_stats(X, bubble_of, nb: int, variant: int = A.BUBBLE_COMBINESTEP, ctx
     ss = A.new_like(XX, (nb, d), np.float64)
     rep = A.new_like(XX, (nb, d), np.float64)
     info = A.new_like(XX, (nb, 3), np.float64)
-    c = _ctx(XX, ctx)
-    A.check(A.lib().hdb_bubble_stats(c.h, XX.p, n, d, bo.p, nb, variant, A.ptr(ls), A.ptr(ss), A.ptr(rep),
-                                     A.ptr(info)), "bubble_stats")
+    c = A.context_for(ctx, XX)
+    A.call("hdb_bubble_stats", c.h, XX.p, n, d, bo.p, nb, variant, A.ptr(ls), A.ptr(ss), A.ptr(rep), A.ptr(info),
+           what="bubble_stats")
     return ls, ss, rep, info
 
 
@@ -153,12 +149,10 @@ class FirstStep:
         ne = int(np.sum(np.where(sizes > 0, 2 * sizes - 1, 0)))
         idsA = A.Arr(ids, np.int32)
         core = A.new_like(XX, (n,), np.float64)
-        va = A.new_like(XX, (ne,), np.int32)
-        vb = A.new_like(XX, (ne,), np.int32)
-        w = A.new_like(XX, (ne,), np.float64)
-        c = _ctx(XX, self.ctx)
-        A.check(A.lib().hdb_leaf_msts(c.h, XX.p, A.ptr(off), P, d, idsA.p, self.mpts, metric_of(self.distanceFunction),
-                                      A.ptr(core), A.ptr(va), A.ptr(vb), A.ptr(w)), "FirstStep.leaf")
+        va, vb, w = A.new_edges(XX, ne)
+        c = A.context_for(self.ctx, XX)
+        A.call("hdb_leaf_msts", c.h, XX.p, A.ptr(off), P, d, idsA.p, self.mpts, metric_of(self.distanceFunction),
+               A.ptr(core), A.ptr(va), A.ptr(vb), A.ptr(w), what="FirstStep.leaf")
         return core, UndirectedGraph(va, vb, w)
 
     def nearest(self, X, x_key=None):
@@ -184,8 +178,8 @@ class LocalModelReduceByKey:
 def sort_edges_desc(va, vb, w, ctx=None):
     """UnionFindReducer + SortMST merge (stable, descending weight), in place."""
     a, b, ww = A.Arr(va, np.int32), A.Arr(vb, np.int32), A.Arr(w, np.float64)
-    c = _ctx(a, ctx)
-    A.check(A.lib().hdb_sort_edges_desc(c.h, a.p, b.p, ww.p, ww.obj.shape[0]), "sort_edges_desc")
+    c = A.context_for(ctx, a)
+    A.call("hdb_sort_edges_desc", c.h, a.p, b.p, ww.p, ww.obj.shape[0], what="sort_edges_desc")
     return a.obj, b.obj, ww.obj
 
 
@@ -196,8 +190,8 @@ def merge_sorted_runs(va, vb, w, run_off, ctx=None):
     a, b, ww = A.Arr(va, np.int32), A.Arr(vb, np.int32), A.Arr(w, np.float64)
     off = np.ascontiguousarray(np.asarray(run_off, np.int64))
     ne = ww.obj.shape[0]
-    oa, ob, ow = A.new_like(a, (ne,), np.int32), A.new_like(a, (ne,), np.int32), A.new_like(a, (ne,), np.float64)
-    c = _ctx(a, ctx)
-    A.check(A.lib().hdb_merge_sorted_runs(c.h, a.p, b.p, ww.p, off.ctypes.data, len(off) - 1, A.ptr(oa), A.ptr(ob),
-                                          A.ptr(ow)), "merge_sorted_runs")
+    oa, ob, ow = A.new_edges(a, ne)
+    c = A.context_for(ctx, a)
+    A.call("hdb_merge_sorted_runs", c.h, a.p, b.p, ww.p, off.ctypes.data, len(off) - 1, A.ptr(oa), A.ptr(ob),
+           A.ptr(ow), what="merge_sorted_runs")
     return oa, ob, ow

@@ -61,23 +61,12 @@ def metric_of(distanceFunction) -> int:
     return A.METRIC[distanceFunction.getName()]
 
 
-def _ctx(ref: A.Arr, ctx=None) -> A.Context:
-    if ctx is not None:
-        return ctx
-    dev = ref.device.index if (ref.device is not None and ref.device.type == "cuda") else 0
-    c = A.Context.get(dev or 0)
-    if ref.device is not None and ref.device.type == "cuda":
-        c.use_torch_stream()
-    return c
-
-
 def distance_rows(a, b, distanceFunction=None, ctx=None):
     aa, bb = A.Arr(a, np.float64), A.Arr(b, np.float64)
     n, d = aa.obj.shape
     out = A.new_like(aa, (n,), np.float64)
-    c = _ctx(aa, ctx)
-    A.check(A.lib().hdb_distance_rows(c.h, aa.p, bb.p, n, d, metric_of(distanceFunction), A.ptr(out)),
-            "hdb_distance_rows")
+    c = A.context_for(ctx, aa)
+    A.call("hdb_distance_rows", c.h, aa.p, bb.p, n, d, metric_of(distanceFunction), A.ptr(out))
     return out
 
 
@@ -101,7 +90,7 @@ class UndirectedGraph:
     def quicksortByEdgeWeight(self):
         """UndirectedGraph.java:93-124 (pivot = startIndex quirk), in place on host copies."""
         a, b, w = self._host()
-        A.check(A.lib().hdb_quicksort_edges(A.ptr(a), A.ptr(b), A.ptr(w), w.shape[0]), "quicksortByEdgeWeight")
+        A.call("hdb_quicksort_edges", A.ptr(a), A.ptr(b), A.ptr(w), w.shape[0], what="quicksortByEdgeWeight")
         self.verticesA, self.verticesB, self.edgeWeights = a, b, w
 
     def getNumVertices(self):
@@ -144,9 +133,9 @@ class HDBSCANStar:
         X = A.Arr(dataSet, np.float64)
         n, d = X.obj.shape
         core = A.new_like(X, (n,), np.float64)
-        c = _ctx(X, self.ctx)
-        A.check(A.lib().hdb_core_distances(c.h, X.p, n, d, k, metric_of(distanceFunction), semantics,
-                                           A.ptr(core)), "calculateCoreDistances")
+        c = A.context_for(self.ctx, X)
+        A.call("hdb_core_distances", c.h, X.p, n, d, k, metric_of(distanceFunction), semantics, A.ptr(core),
+               what="calculateCoreDistances")
         return core
 
     def constructMST(self, dataSet, coreDistances, selfEdges: bool, distanceFunction=None, indices=None,
@@ -157,12 +146,10 @@ class HDBSCANStar:
         core = A.Arr(coreDistances, np.float64)
         ids = A.Arr(indices, np.int32) if indices is not None else None
         ne = (n - 1) + (n if selfEdges else 0)
-        va = A.new_like(X, (ne,), np.int32)
-        vb = A.new_like(X, (ne,), np.int32)
-        w = A.new_like(X, (ne,), np.float64)
-        c = _ctx(X, self.ctx)
-        A.check(A.lib().hdb_prim_mst(c.h, X.p, n, d, core.p, ids.p if ids else None, metric_of(distanceFunction),
-                                     int(bool(selfEdges)), A.ptr(va), A.ptr(vb), A.ptr(w)), "constructMST")
+        va, vb, w = A.new_edges(X, ne)
+        c = A.context_for(self.ctx, X)
+        A.call("hdb_prim_mst", c.h, X.p, n, d, core.p, ids.p if ids else None, metric_of(distanceFunction),
+               int(bool(selfEdges)), A.ptr(va), A.ptr(vb), A.ptr(w), what="constructMST")
         return UndirectedGraph(va, vb, w)
 
     def constructLocalMST(self, dataSet, indices, coreDistances, selfEdges: bool, distanceFunction=None,
@@ -178,9 +165,9 @@ class HDBSCANStar:
         a, b, ww = A.Arr(va, np.int32), A.Arr(vb, np.int32), A.Arr(w, np.float64)
         ne = a.obj.shape[0]
         f1, f2, nd = (A.new_like(a, (ne,), np.int32) for _ in range(3))
-        c = _ctx(a, self.ctx)
-        A.check(A.lib().hdb_local_mst_ids(c.h, ids.p if ids else None, n, a.p, b.p, ww.p, ne, int(node), A.ptr(f1),
-                                          A.ptr(f2), A.ptr(nd)), "hdb_local_mst_ids")
+        c = A.context_for(self.ctx, a)
+        A.call("hdb_local_mst_ids", c.h, ids.p if ids else None, n, a.p, b.p, ww.p, ne, int(node), A.ptr(f1),
+               A.ptr(f2), A.ptr(nd))
         return va, vb, w, f1, f2, nd
 
     def constructMSTBoruvka(self, dataSet, coreDistances, selfEdges: bool, distanceFunction=None) -> UndirectedGraph:
@@ -193,12 +180,10 @@ class HDBSCANStar:
         n, d = X.obj.shape
         core = A.Arr(coreDistances, np.float64)
         ne = (n - 1) + (n if selfEdges else 0)
-        va = A.new_like(X, (ne,), np.int32)
-        vb = A.new_like(X, (ne,), np.int32)
-        w = A.new_like(X, (ne,), np.float64)
-        c = _ctx(X, self.ctx)
-        A.check(A.lib().hdb_mst_boruvka(c.h, X.p, n, d, core.p, metric_of(distanceFunction), int(bool(selfEdges)),
-                                        A.ptr(va), A.ptr(vb), A.ptr(w)), "constructMSTBoruvka")
+        va, vb, w = A.new_edges(X, ne)
+        c = A.context_for(self.ctx, X)
+        A.call("hdb_mst_boruvka", c.h, X.p, n, d, core.p, metric_of(distanceFunction), int(bool(selfEdges)),
+               A.ptr(va), A.ptr(vb), A.ptr(w), what="constructMSTBoruvka")
         return UndirectedGraph(va, vb, w)
 
     def exactMST(self, dataSet, k: int, distanceFunction=None, semantics: int = A.CORE_EXCL_SELF,
@@ -214,13 +199,11 @@ class HDBSCANStar:
         n, d = X.obj.shape
         ne = (n - 1) + (n if selfEdges else 0)
         core = A.new_like(X, (n,), np.float64)
-        va = A.new_like(X, (ne,), np.int32)
-        vb = A.new_like(X, (ne,), np.int32)
-        w = A.new_like(X, (ne,), np.float64)
-        c = _ctx(X, self.ctx)
+        va, vb, w = A.new_edges(X, ne)
+        c = A.context_for(self.ctx, X)
         flags = (A.EDGES_SELF if selfEdges else 0) | (A.EDGES_MERGED if merged else 0)
-        A.check(A.lib().hdb_exact_mst(c.h, X.p, n, d, k, metric_of(distanceFunction), semantics, flags,
-                                      A.ptr(core), A.ptr(va), A.ptr(vb), A.ptr(w)), "exactMST")
+        A.call("hdb_exact_mst", c.h, X.p, n, d, k, metric_of(distanceFunction), semantics, flags, A.ptr(core),
+               A.ptr(va), A.ptr(vb), A.ptr(w), what="exactMST")
         return core, UndirectedGraph(va, vb, w)
 
     def knn(self, dataSet, k: int, distanceFunction=None, exclSelf: bool = False, withIndices: bool = False):
@@ -229,9 +212,9 @@ class HDBSCANStar:
         n, d = X.obj.shape
         dist = A.new_like(X, (n, k), np.float64)
         idx = A.new_like(X, (n, k), np.int32) if withIndices else None
-        c = _ctx(X, self.ctx)
-        A.check(A.lib().hdb_knn(c.h, X.p, n, d, k, metric_of(distanceFunction), int(exclSelf), A.ptr(dist),
-                                A.ptr(idx)), "knn")
+        c = A.context_for(self.ctx, X)
+        A.call("hdb_knn", c.h, X.p, n, d, k, metric_of(distanceFunction), int(exclSelf), A.ptr(dist), A.ptr(idx),
+               what="knn")
         return (dist, idx) if withIndices else dist
 
     def attachPoints(self, dataSet, coreDistances, queries, k: int, distanceFunction=None, attach_splits: int = 0):
@@ -253,11 +236,9 @@ class HDBSCANStar:
             raise ValueError("coreDistances must have one entry per training row")
         core_q, level = A.new_like(Q, (m,), np.float64), A.new_like(Q, (m,), np.float64)
         nearest = A.new_like(Q, (m,), np.int32)
-        ref = next((x for x in (Q, X, core) if x.device is not None and x.device.type == "cuda"), Q)
-        c = _ctx(ref, self.ctx)
-        A.check(A.lib().hdb_attach_points_splits(c.h, X.p, n, d, core.p, Q.p, m, k, metric_of(distanceFunction),
-                                                 int(attach_splits), A.ptr(core_q), A.ptr(nearest), A.ptr(level)),
-                "attachPoints")
+        c = A.context_for(self.ctx, Q, X, core)
+        A.call("hdb_attach_points_splits", c.h, X.p, n, d, core.p, Q.p, m, k, metric_of(distanceFunction),
+               int(attach_splits), A.ptr(core_q), A.ptr(nearest), A.ptr(level), what="attachPoints")
         return core_q, nearest, level
 
 
@@ -270,10 +251,9 @@ def flat_labels(va, vb, w, n: int, minClSize: int, ctx=None):
     a, b, ww = A.Arr(va, np.int32), A.Arr(vb, np.int32), A.Arr(w, np.float64)
     labels = A.new_like(a, (n,), np.int32)
     k = np.zeros(1, np.int64)
-    on_dev = a.device is not None and a.device.type == "cuda"
-    h = ctx.h if ctx is not None else (A.Context.get(a.device.index or 0).h if on_dev else None)
-    A.check(A.lib().hdb_flat_labels(h, a.p, b.p, ww.p, ww.obj.shape[0], n, minClSize, A.ptr(labels), A.ptr(k)),
-            "flat_labels")
+    c = A.context_for(ctx, a, host_ok=True)
+    A.call("hdb_flat_labels", c.h if c else None, a.p, b.p, ww.p, ww.obj.shape[0], n, minClSize, A.ptr(labels),
+           A.ptr(k), what="flat_labels")
     return labels, int(k[0])
 
 
@@ -294,11 +274,9 @@ def outlier_scores(va, vb, w, n: int, minClSize: int, ctx=None, with_labels: boo
     noise = A.new_like(a, (n,), np.float64)
     labels = A.new_like(a, (n,), np.int32) if with_labels else None
     k = np.zeros(1, np.int64)
-    on_dev = a.device is not None and a.device.type == "cuda"
-    h = ctx.h if ctx is not None else (A.Context.get(a.device.index or 0).h if on_dev else None)
-    A.check(A.lib().hdb_flat_outlier_scores(h, a.p, b.p, ww.p, ww.obj.shape[0], n, minClSize, A.ptr(scores),
-                                            A.ptr(noise), A.ptr(labels), A.ptr(k) if with_labels else None),
-            "outlier_scores")
+    c = A.context_for(ctx, a, host_ok=True)
+    A.call("hdb_flat_outlier_scores", c.h if c else None, a.p, b.p, ww.p, ww.obj.shape[0], n, minClSize, A.ptr(scores),
+           A.ptr(noise), A.ptr(labels), A.ptr(k) if with_labels else None, what="outlier_scores")
     return (scores, noise, labels, int(k[0])) if with_labels else (scores, noise)
 
 
@@ -390,11 +368,6 @@ class ClusterTree:
         return self._back(torch.where(eps == 0, torch.zeros_like(eps), 1.0 - e / eps))
 
 
-def _flat_handle(a, ctx):
-    on_dev = a.device is not None and a.device.type == "cuda"
-    return ctx.h if ctx is not None else (A.Context.get(a.device.index or 0).h if on_dev else None)
-
-
 def cluster_tree_bound(n: int, minClSize: int) -> int:
     """hdb_cluster_tree_bound: max(1, 2 * (n // minClSize) - 1) clusters at most (0 for n <= 0)."""
     return int(A.lib().hdb_cluster_tree_bound(int(n), int(minClSize)))
@@ -412,10 +385,10 @@ def cluster_tree(va, vb, w, n: int, minClSize: int, ctx=None) -> ClusterTree:
     f64 = [A.new_like(a, (cap,), np.float64) for _ in range(3)]
     pc, pl = A.new_like(a, (n,), np.int32), A.new_like(a, (n,), np.float64)
     kt, k = np.zeros(1, np.int64), np.zeros(1, np.int64)
-    A.check(A.lib().hdb_flat_cluster_tree(_flat_handle(a, ctx), a.p, b.p, ww.p, ww.obj.shape[0], n, minClSize, cap,
-                                          A.ptr(kt), A.ptr(i32[0]), A.ptr(f64[0]), A.ptr(f64[1]), A.ptr(f64[2]),
-                                          A.ptr(i32[1]), A.ptr(i32[2]), A.ptr(i32[3]), A.ptr(pc), A.ptr(pl), A.ptr(k)),
-            "cluster_tree")
+    c = A.context_for(ctx, a, host_ok=True)
+    A.call("hdb_flat_cluster_tree", c.h if c else None, a.p, b.p, ww.p, ww.obj.shape[0], n, minClSize, cap, A.ptr(kt),
+           A.ptr(i32[0]), A.ptr(f64[0]), A.ptr(f64[1]), A.ptr(f64[2]), A.ptr(i32[1]), A.ptr(i32[2]), A.ptr(i32[3]),
+           A.ptr(pc), A.ptr(pl), A.ptr(k), what="cluster_tree")
     K = int(kt[0])
     return ClusterTree(i32[0][:K], f64[0][:K], f64[1][:K], f64[2][:K], i32[1][:K], i32[2][:K], i32[3][:K], pc, pl,
                        int(k[0]))
@@ -431,13 +404,9 @@ def labels_at_levels(tree: ClusterTree, levels, ctx=None):
     lv = A.Arr(levels if A.is_torch(levels) else np.atleast_1d(np.asarray(levels, dtype=np.float64)), np.float64)
     L, n, K = int(lv.obj.shape[0]), int(pc.obj.shape[0]), int(par.obj.shape[0])
     out = A.new_like(pc, (L, n), np.int32)
-    h = ctx.h if ctx is not None else None
-    if h is None:
-        for x in (pc, par, lv):
-            if x.device is not None and x.device.type == "cuda":
-                h = A.Context.get(x.device.index or 0).h
-                break
-    A.check(A.lib().hdb_labels_at_levels(h, par.p, bi.p, K, pc.p, pl.p, n, lv.p, L, A.ptr(out)), "labels_at_levels")
+    c = A.context_for(ctx, pc, par, lv, host_ok=True)
+    A.call("hdb_labels_at_levels", c.h if c else None, par.p, bi.p, K, pc.p, pl.p, n, lv.p, L, A.ptr(out),
+           what="labels_at_levels")
     return out
 
 
@@ -457,14 +426,9 @@ def predict_labels(tree: ClusterTree, nearest, level, flat_label=None, ctx=None)
         raise ValueError("flat_label needs one entry per cluster, level one per query")
     tl, lab = A.new_like(nr, (m,), np.int32), A.new_like(nr, (m,), np.int32)
     sc = A.new_like(nr, (m,), np.float64)
-    h = ctx.h if ctx is not None else None
-    if h is None:
-        for x in (nr, lv, pc, par, fl):
-            if x.device is not None and x.device.type == "cuda":
-                h = A.Context.get(x.device.index or 0).h
-                break
-    A.check(A.lib().hdb_predict_labels(h, par.p, bi.p, de.p, fl.p, K, pc.p, pl.p, n, nr.p, lv.p, m, A.ptr(tl),
-                                       A.ptr(lab), A.ptr(sc)), "predict_labels")
+    c = A.context_for(ctx, nr, lv, pc, par, fl, host_ok=True)
+    A.call("hdb_predict_labels", c.h if c else None, par.p, bi.p, de.p, fl.p, K, pc.p, pl.p, n, nr.p, lv.p, m,
+           A.ptr(tl), A.ptr(lab), A.ptr(sc), what="predict_labels")
     return tl, lab, sc
 
 
@@ -529,13 +493,7 @@ def constrained_flat_labels(tree: ClusterTree, ca, cb, ctype, ctx=None) -> Const
     pst = A.new_like(par, (K,), np.float64)
     labels = A.new_like(pc, (n,), np.int32)
     k = np.zeros(1, np.int64)
-    h = ctx.h if ctx is not None else None
-    if h is None:
-        for x in (pc, par, st, mi, a, b, t):
-            if x.device is not None and x.device.type == "cuda":
-                h = A.Context.get(x.device.index or 0).h
-                break
-    A.check(A.lib().hdb_constrained_flat_labels(h, par.p, st.p, mi.p, K, pc.p, n, a.p, b.p, t.p, m, A.ptr(num),
-                                                A.ptr(prop), A.ptr(pst), A.ptr(flat), A.ptr(labels), A.ptr(k)),
-            "constrained_flat_labels")
+    c = A.context_for(ctx, pc, par, st, mi, a, b, t, host_ok=True)
+    A.call("hdb_constrained_flat_labels", c.h if c else None, par.p, st.p, mi.p, K, pc.p, n, a.p, b.p, t.p, m,
+           A.ptr(num), A.ptr(prop), A.ptr(pst), A.ptr(flat), A.ptr(labels), A.ptr(k), what="constrained_flat_labels")
     return ConstrainedLabels(labels, int(k[0]), flat, num, prop, pst, m)

@@ -2,10 +2,11 @@
 // labels), csrc/formats.cpp (record formats), csrc/local_model.cpp (bubble core epilogue,
 // UndirectedGraph quicksort, cluster tree, FOSC + noise reassignment), csrc/inf_edges.cpp (the
 // exact leaf's infinite-weight tail, against an all-pairs Kruskal), and common.hpp's Carver (the
-// bump allocator every device scratch layout goes through).  Built by
+// bump allocator every device scratch layout goes through); with --options, csrc/options.cpp (the
+// option table and the HDB_OPTS parser).  Built by
 // tests/sanitize/Makefile (hipcc --cuda-host-only -fsanitize=address,undefined) and run by
 // tests/test_sanitizers.py on tie-heavy seeded inputs and malformed records.  The library's
-// error setter lives in context.cpp (HIP runtime); a host stub stands in for it here.
+// error message lives in context.cpp (HIP runtime); a host stub stands in for it here.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -17,7 +18,9 @@
 #include "internal.hpp"
 
 namespace hdb {
-void set_error(const std::string &) {}
+static thread_local std::string g_error;
+void set_error(const std::string &msg) { g_error = msg; }
+const char *last_error() { return g_error.c_str(); }
 }  // namespace hdb
 
 // the library's C-ABI wrapper (guarded) turns hdb::Error into a status code; do the same
@@ -293,7 +296,56 @@ static bool carver() {
     return ok;
 }
 
-int main() {
+// --options NAME...: the accept matrix of hdb_ctx_set_option (csrc/options.cpp) on a default-constructed
+// context.  One line per (name, probe): the status, the message if any and, when a field of the
+// context changed, its position in the declaration order of the option fields and its new value.
+// Then HDB_OPTS strings through apply_opts: status and message.  tests/golden/option_accept.txt
+// holds the output of the if-chain this table replaced.
+static int options_matrix(int argc, char **argv) {
+    auto fields = [](const hdb_ctx &c) {
+        return std::vector<int64_t>{
+            c.force_fp64, c.knn_tree, c.knn_tree_min_n, c.knn_mfma, c.knn_mfma_min_n, c.knn_mfma_single,
+            c.knn_mfma_prune, c.nearest_grouped, c.boruvka_seed, c.leaf_seed_k, c.leaf_list_rounds,
+            c.boruvka_knn_seed, c.boruvka_wave_pts, c.boruvka_early_pts, c.boruvka_early_rounds,
+            c.boruvka_adj_seed, c.bor_xcd_chunks, c.k1t_xcd_chunks, c.trav_pop_test, c.prim_coop,
+            c.prim_coop_plain, c.bubble_fold_dim, c.bubble_knn_split, c.prim_coop_xcd, c.prim_coop_bs,
+            c.prim_coop_plain_spin_log2, c.prim_coop_slots, c.flat_link_variant, c.flat_root_variant,
+            c.flat_relabel, c.flat_block_log, c.flat_mid_log, c.flat_deep_depth, c.flat_deep_root,
+            c.flat_deep_link, c.ssort, c.ssort_cap, c.count_evals};
+    };
+    const int64_t two31 = int64_t(1) << 31;
+    const int64_t probes[] = {-two31 - 1, -two31, -2,  -1,  0,   1,   2,   3,    4,    5,    6,    7,     8,         9,
+                              10,         11,     12,  16,  24,  25,  31,  32,   63,   64,   65,   127,   128,       129,
+                              256,        512,    1023, 1024, 1025, 4096, 4097, two31 - 1, two31, int64_t(1) << 40};
+    for (int i = 0; i < argc; i++)
+        for (int64_t v : probes) {
+            hdb_ctx c;
+            const std::vector<int64_t> before = fields(c);
+            hdb::set_error("");
+            const int rc = hdb_ctx_set_option(&c, argv[i], v);
+            printf("%s %lld -> %d '%s'", argv[i], (long long)v, rc, hdb::last_error());
+            const std::vector<int64_t> after = fields(c);
+            for (size_t f = 0; f < after.size(); f++)
+                if (after[f] != before[f]) printf(" field %zu = %lld", f, (long long)after[f]);
+            printf("\n");
+        }
+    hdb_ctx c;
+    printf("null ctx %d, null name %d\n", hdb_ctx_set_option(nullptr, "ssort", 1), hdb_ctx_set_option(&c, nullptr, 1));
+    const char *opts[] = {"flat_block_log=7", "no_such=1", "flat_block_log", "knn_tree_min_n=99999999999999999999",
+                          "", ",,", "flat_block_log=9,", "=1", "ssort=0,flat_mid_log=3,,ssort_cap=4097,ssort=1",
+                          "ssort= 1", "ssort=1x", "ssort=", "flat_deep_depth=-1"};
+    for (const char *o : opts) {
+        hdb_ctx k;
+        hdb::set_error("");
+        const int rc = hdb::apply_opts(&k, o);
+        printf("opts '%s' -> %d '%s' ssort %d block_log %d mid_log %d\n", o, rc, hdb::last_error(), (int)k.ssort,
+               k.flat_block_log, k.flat_mid_log);
+    }
+    return 0;
+}
+
+int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "--options")) return options_matrix(argc - 2, argv + 2);
     if (!carver()) return 1;
     // K6 relabel limit (flat.hip): contracted labels nv + rank < 3m must fit int32
     if (!hdb::flat_relabel_fits(715827882) || hdb::flat_relabel_fits(715827883) || !hdb::flat_relabel_fits(0)) {

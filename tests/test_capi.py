@@ -25,6 +25,55 @@ def test_library_exports_every_header_symbol(pkg):
     assert set(syms) == set(pkg._capi.EXPORTED)
 
 
+def header_prototypes():
+    """{name: (return kind, [parameter kinds])} of include/hdbmi.h; a kind is ptr, i32, i64, f64 or void"""
+    src = open(os.path.join(ROOT, "include", "hdbmi.h")).read()
+    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
+    src = re.sub(r"//[^\n]*|^\s*#[^\n]*", " ", src, flags=re.M)
+
+    def kind(decl):
+        decl = decl.strip()
+        if "*" in decl:
+            return "ptr"
+        base = re.sub(r"\bconst\b", "", decl).split()[0]
+        return {"int": "i32", "int32_t": "i32", "int64_t": "i64", "double": "f64", "void": "void"}[base]
+
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s]*?[\s*]+)(hdb_\w+)\s*\(([^()]*)\)\s*;", src):
+        params = [] if params.strip() == "void" else params.split(",")
+        # a parameter's kind is that of its type: the declaration without the trailing name
+        protos[name] = (kind(ret), [kind(re.sub(r"\w+\s*$", "", p)) for p in params])
+    return protos
+
+
+def ctypes_kind(t):
+    if t is None:
+        return "void"
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer):
+        return "ptr"
+    if t is ctypes.c_double:
+        return "f64"
+    assert issubclass(t, ctypes._SimpleCData) and t._type_ in "ilq", t  # signed integers
+    return {4: "i32", 8: "i64"}[ctypes.sizeof(t)]
+
+
+def test_binding_table_matches_the_header(pkg):
+    """every prototype of hdbmi.h has a row in _capi.SIGNATURES with the same number of
+    parameters, each of the same kind (pointer, 32-bit int, 64-bit int, double), and the same
+    kind of return value: a parameter added in C and forgotten in Python fails here"""
+    protos = header_prototypes()
+    table = pkg._capi.SIGNATURES
+    assert set(protos) == set(header_symbols()) == set(table)
+    assert pkg._capi.EXPORTED == list(table)
+    bad = {}
+    for name, (ret, params) in protos.items():
+        restype, argtypes = table[name]
+        got = (ctypes_kind(restype), [ctypes_kind(t) for t in argtypes])
+        if got != (ret, params):
+            bad[name] = (got, (ret, params))
+    assert not bad, bad
+
+
 def test_no_device_raises_loudly(pkg):
     try:
         import torch

@@ -1,4 +1,4 @@
-"""The option table of hdb_ctx_set_option (csrc/context.cpp), the defaults the tests restore
+"""The option table of hdb_ctx_set_option (csrc/options.cpp), the defaults the tests restore
 (path_helpers.DEFAULTS) and DESIGN.md's table of where each option is pinned name the same
 options: a new option without a test row, or a removed one still listed, fails here."""
 import os
@@ -9,10 +9,10 @@ from path_helpers import DEFAULTS
 
 
 def accepted_options():
-    with open(os.path.join(ROOT, PKG_NAME, "csrc", "context.cpp")) as fh:
+    with open(os.path.join(ROOT, PKG_NAME, "csrc", "options.cpp")) as fh:
         src = fh.read()
-    body = src[src.index("int hdb_ctx_set_option("):src.index("int hdb_ctx_get_stat(")]
-    return set(re.findall(r'k == "([a-z0-9_]+)"', body))
+    table = src[src.index("const Option OPTIONS[] = {"):src.index("}  // namespace")]
+    return set(re.findall(r'^    \{"([a-z0-9_]+)", ', table, re.M))
 
 
 def test_defaults_cover_the_option_table():
