@@ -367,9 +367,17 @@ class MRHDBSCANStar:
             lo, hi = P.chunk(brows.shape[0], world, rank)  # this rank's points (all of them at N = 1)
             nearest = torch.empty(hi - lo, dtype=torch.int32, device=dev)
             if hi > lo:
+                ndist = torch.empty(hi - lo, dtype=torch.float64, device=dev)
                 A.check(A.lib().hdb_nearest_sample(c.h, Xb[lo:hi].data_ptr(), hi - lo, S.data_ptr(), S.shape[0], d,
                                                    self.metric, bkey_local[lo:hi].data_ptr(), s_key.data_ptr(),
-                                                   nearest.data_ptr(), None), "FirstStep.nearest")
+                                                   nearest.data_ptr(), ndist.data_ptr()), "FirstStep.nearest")
+                # a point without a candidate (every distance to its subset's samples NaN or not
+                # below Double.MAX_VALUE: a zero row under cosine) keeps FirstStep's initial
+                # nearest = 0, the first sample of ITS OWN subset's list (D3: the scan runs per
+                # subset); the call reports position 0 of the level's concatenated list, which
+                # belongs to the first subset
+                first = torch.tensor(s_off[:-1], dtype=torch.int32, device=dev)
+                nearest = torch.where(ndist == A.JMAX, first[bkey_local[lo:hi].long()], nearest)
             if world > 1:
                 nearest = P.allgather_var(nearest, self.group)
             if self.profile:

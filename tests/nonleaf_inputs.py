@@ -129,6 +129,114 @@ def global_box_case(d):
     return ro(X, S, idx, dist)
 
 
+# ------------------------------------------------------- keyed nearest sample under every metric
+ALL_METRICS = ["euclidean"] + METRICS
+KM_DIMS = (1, 2, 3, 7, 8, 9, 24)          # 1, 2, 3, 8: a fast Euclidean instantiation; 7, 9, 24: none
+KM_FAST_DIMS = (1, 2, 3, 4, 5, 6, 8, 16)  # nearest.hip nearest_sample_device(): fast = Euclidean and one of these
+KM_KEYS = (3, 11, 5, 40, 7, 2, 19)        # unsorted; 40 has points but no sample, 7 a single sample
+KM_NO_SAMPLE, KM_ONE_SAMPLE, KM_DUP, KM_COPY = 40, 7, 5, 2
+# name: (key set, n, m).  one: a single key; seven: KM_KEYS interleaved, two samples of key 5 repeated
+# later in the list under key 5, and one sample of key 5 copied to an EARLIER list position under key 2
+# (same distance to every point, a foreign key, first in sample order: it must not win); zero: seven
+# with two zero rows among the points and two among the samples; rays: seven on metric_kruskal.rays
+KM_SHAPES = {
+    "one-1x1": ("one", 1, 1), "one-1x300": ("one", 1, 300), "one-255x1": ("one", 255, 1),
+    "one-257x64": ("one", 257, 64), "one-1500x300": ("one", 1500, 300),
+    "seven-255x64": ("seven", 255, 64), "seven-257x300": ("seven", 257, 300), "seven-1500x64": ("seven", 1500, 64),
+    "seven-1500x300": ("seven", 1500, 300),
+    "zero-257x64": ("zero", 257, 64), "zero-1500x300": ("zero", 1500, 300),
+    "rays-255x300": ("rays", 255, 300), "rays-1500x64": ("rays", 1500, 64),
+}
+
+
+def km_scan(metric, d):
+    """the timer name of the scan nearest_sample_device() launches below K3g's thresholds"""
+    return "nearest_sq" if metric == "euclidean" and d in KM_FAST_DIMS else "nearest_generic"
+
+
+@functools.lru_cache(maxsize=None)
+def _km_input(name, d):
+    """(X, S, x_key, s_key, slots): the same rows and keys for every metric"""
+    from metric_kruskal import rays
+    kind, n, m = KM_SHAPES[name]
+    rng = np.random.default_rng(7000 + 31 * d + 7 * n + m)
+    if kind == "rays":
+        Z = rays(n + m, d)
+    else:  # rounded to 0.1: distances tie at small d
+        C = rng.uniform(-4.0, 4.0, size=(5, d))
+        Z = np.round(C[rng.integers(0, 5, n + m)] + rng.normal(0, 1.0, size=(n + m, d)), 1)
+    X, S = np.ascontiguousarray(Z[:n]), np.ascontiguousarray(Z[n:])
+    if kind == "one":
+        return ro(X, S, np.full(n, 9, np.int32), np.full(m, 9, np.int32)) + ({},)
+    keys = np.array(KM_KEYS, np.int32)
+    xk = keys[rng.integers(0, 7, n)]
+    xk[:7] = keys[rng.permutation(7)]                      # every key has a point
+    sk = keys[[0, 1, 2, 5, 6]][rng.integers(0, 5, m)]      # 40 and 7 left out
+    sk[:5] = keys[[5, 0, 6, 1, 2]]                         # key 2 first: an early slot for the copy
+    sk[m // 2] = KM_ONE_SAMPLE
+    slots = {}
+    if kind == "zero":
+        z = [int(np.flatnonzero(sk == 3)[0]), int(np.flatnonzero(sk == 19)[-1])]
+        S[z] = 0.0
+        X[[np.flatnonzero(xk == 11)[0], np.flatnonzero(xk == 3)[-1]]] = 0.0  # keys that have samples
+        slots["zero_samples"] = z
+    a = np.flatnonzero(sk == KM_DUP)
+    assert a.shape[0] >= 6
+    S[a[-1]], S[a[-2]] = S[a[0]], S[a[1]]                  # repeated inside the key: the first must win
+    c = int(a[a.shape[0] // 2])
+    e = int(np.flatnonzero(sk == KM_COPY)[0])
+    assert e < c
+    S[e] = S[c]                                            # the same row under a foreign key, earlier in the list
+    p = int(np.flatnonzero(xk == KM_DUP)[0])
+    X[p] = S[c]                                            # a point of key 5 on it
+    slots.update(dup=[(int(a[0]), int(a[-1])), (int(a[1]), int(a[-2]))], copy=(c, e), on_copy=p)
+    return ro(X, S, xk, sk) + (slots,)
+
+
+@functools.lru_cache(maxsize=None)
+def keyed_metric_case(name, metric, d):
+    """(X, S, x_key, s_key, oracle index, oracle distance, traits) of the keyed call.  traits counts,
+    with the oracle alone, what the input holds:
+      no_sample     rows whose key has no sample
+      nan_pairs     (row, sample of its key) pairs whose distance is NaN: one of the two has a NaN
+                    distance to itself (zero norm under cosine, zero variance under Pearson)
+      all_nan       rows whose key has samples, all of them at a NaN distance
+      no_candidate  rows the oracle left at index 0 and Double.MAX_VALUE
+      tied          rows whose minimum is reached by more than one sample of their key (the scan
+                    over the reversed list ends at another sample)
+      unkeyed_differs  rows on which the unkeyed scan picks another sample (a missing key filter shows)
+      foreign_nearer   rows with a foreign sample strictly nearer than the chosen one
+      foreign_first    rows with a foreign sample at the same distance, earlier in the list
+      distinct      distinct distances among the rows that have a candidate"""
+    from oracle import oracle as O
+    X, S, xk, sk, slots = _km_input(name, d)
+    n, m = X.shape[0], S.shape[0]
+    idx, dist = O.nearest_sample(X, S, metric, x_key=xk, s_key=sk)
+    ridx, rdist = O.nearest_sample(X, S[::-1], metric, x_key=xk, s_key=sk[::-1])
+    uidx, udist = O.nearest_sample(X, S, metric)
+    assert bits_same(dist, rdist)
+    has = dist < O.JMAX
+    bad_x = np.array([np.isnan(O.distance(r, r, metric)) for r in X])
+    bad_s = np.array([np.isnan(O.distance(r, r, metric)) for r in S])
+    cnt = {int(k): int((sk == k).sum()) for k in np.unique(xk)}
+    cnt_bad = {int(k): int(((sk == k) & bad_s).sum()) for k in np.unique(xk)}
+    own = np.array([cnt[int(k)] for k in xk])
+    own_nan = np.where(bad_x, own, np.array([cnt_bad[int(k)] for k in xk]))
+    foreign = sk[uidx] != xk
+    traits = dict(no_sample=int((own == 0).sum()), nan_pairs=int(own_nan.sum()),
+                  all_nan=int(((own > 0) & (own_nan == own)).sum()), no_candidate=int((~has).sum()),
+                  tied=int((has & (m - 1 - ridx != idx)).sum()), unkeyed_differs=int((uidx != idx).sum()),
+                  foreign_nearer=int((has & foreign & (udist < dist)).sum()),
+                  foreign_first=int((has & foreign & (udist == dist) & (uidx < idx)).sum()),
+                  distinct=int(np.unique(dist[has]).shape[0]), slots=slots)
+    return ro(X, S, xk, sk, idx, dist) + (traits,)
+
+
+def bits_same(a, b):
+    na, nb = np.isnan(a), np.isnan(b)
+    return np.array_equal(na, nb) and np.array_equal(a[~na], b[~nb])
+
+
 # ------------------------------------------------------------------------------------ bubbles
 def compact(near, m):
     """bubble ids 0..nb-1 of the samples some point chose, in sample order (tests/golden/make_golden.py)"""

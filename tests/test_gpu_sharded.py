@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch.multiprocessing as mp
 
+import driver_cases
 from conftest import blobs, check_driver_structure, golden, load_skin
 
 pytestmark = pytest.mark.gpu
@@ -35,6 +36,12 @@ CASES = {
     # two well-separated blobs: level 0's one local model splits them into two leaves, so at
     # world 4 two ranks get no leaf and three no local model
     "few_leaves": dict(data=lambda: blobs(6000, 3, 2, 9), processing_units=4000, samples_per_subset=300),
+    # tests/driver_cases.py: levels with several big subsets under a non-Euclidean metric (the keyed
+    # generic nearest-sample scan in point chunks, the metric's local models dealt by LPT), minPts 8
+    "ang5_cosine": dict(data=lambda: np.array(driver_cases.input_of("ang5")), processing_units=300, k=0.1,
+                        distanceFunction="cosine"),
+    "d7r_manhattan": dict(data=lambda: np.array(driver_cases.input_of("d7r")), processing_units=300, k=0.1,
+                          distanceFunction="manhattan", minPts=8, minClSize=8, bubble_slices=8),
 }
 LAZY = {"c5s": _c5s_case}
 
@@ -85,7 +92,7 @@ def _worker(rank, world, port, name, out_dir):
 
 
 @pytest.mark.parametrize("name,world", [("skin_prefix", 2), ("c3_shaped", 2), ("c3_shaped", 3), ("few_leaves", 4),
-                                        ("c5s", 3), ("c5s", 4)])
+                                        ("c5s", 3), ("c5s", 4), ("ang5_cosine", 2), ("d7r_manhattan", 2)])
 def test_sharded_driver_equals_single_device(pkg, name, world, tmp_path):
     """world 3 / 4 on the scaled-C5 fixture: every rank's merged list equals the oracle's
     MR-HDBSCAN* bit for bit (reference-Prim leaves), levels and bubble labels included.  The
