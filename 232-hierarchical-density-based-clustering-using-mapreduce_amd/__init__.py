@@ -18,6 +18,7 @@ from .hdbscanstar import (CosineSimilarity, DistanceCalculator, EuclideanDistanc
                           ManhattanDistance, PearsonCorrelation, SupremumDistance, UndirectedGraph,
                           ClusterTree, ConstrainedLabels, Prediction, approximate_predict, cluster_tree,
                           cluster_tree_bound, constrained_flat_labels, distance_rows, flat_labels,
-                          labels_at_levels, outlier_ranking, outlier_scores, predict_labels)
+                          labels_at_levels, outlier_ranking, outlier_scores, predict_labels,
+                          Validity, validity_index)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

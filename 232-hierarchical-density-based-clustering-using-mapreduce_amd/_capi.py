@@ -81,6 +81,12 @@ SIGNATURES = {
     "hdb_nearest_sample": (_int, [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "hdb_attach_points": (_int, [_vp, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "hdb_attach_points_splits": (_int, [_vp, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "hdb_validity_index": (_int, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, C.POINTER(C.c_double), _vp, _vp, _vp, _vp, _vp,
+                                  _vp, _vp]),
+    "hdb_validity_index_splits": (_int, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, C.POINTER(C.c_double), _vp, _vp,
+                                         _vp, _vp, _vp, _vp, _vp]),
+    "hdb_validity_index_route": (_int, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _i32, C.POINTER(C.c_double), _vp,
+                                        _vp, _vp, _vp, _vp, _vp, _vp]),
     "hdb_bubble_stats": (_int, [_vp, _vp, _i64, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "hdb_bubble_partials": (_int, [_vp, _vp, _i64, _i32, _vp, _i64, _vp, _i32, _vp, _vp, _vp]),
     "hdb_bubble_combine": (_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp]),

@@ -302,6 +302,59 @@ int hdb_attach_points_splits(hdb_ctx *ctx, const double *X, int64_t n, int32_t d
     });
 }
 
+int hdb_validity_index(hdb_ctx *ctx, const double *X, int64_t n, int32_t d, const int32_t *labels, int32_t K,
+                       int32_t metric, double *index, double *validity, double *sparseness, double *separation,
+                       int32_t *nearest_cluster, int32_t *size, double *apts_core, int32_t *internal) {
+    return hdb_validity_index_route(ctx, X, n, d, labels, K, metric, 0, HDB_VALIDITY_SMALL_MAX, index, validity,
+                                    sparseness, separation, nearest_cluster, size, apts_core, internal);
+}
+
+int hdb_validity_index_splits(hdb_ctx *ctx, const double *X, int64_t n, int32_t d, const int32_t *labels, int32_t K,
+                              int32_t metric, int32_t splits, double *index, double *validity, double *sparseness,
+                              double *separation, int32_t *nearest_cluster, int32_t *size, double *apts_core,
+                              int32_t *internal) {
+    return hdb_validity_index_route(ctx, X, n, d, labels, K, metric, splits, HDB_VALIDITY_SMALL_MAX, index, validity,
+                                    sparseness, separation, nearest_cluster, size, apts_core, internal);
+}
+
+int hdb_validity_index_route(hdb_ctx *ctx, const double *X, int64_t n, int32_t d, const int32_t *labels, int32_t K,
+                             int32_t metric, int32_t splits, int32_t small_max, double *index, double *validity,
+                             double *sparseness, double *separation, int32_t *nearest_cluster, int32_t *size,
+                             double *apts_core, int32_t *internal) {
+    return guarded(ctx, [&] {
+        check_metric(metric);
+        if (splits < 0 || splits > 65535) HDB_THROW(HDB_EINVAL, "validity: splits must be in 0..65535");
+        if (n < 0 || d <= 0 || K < 0 || !index || (n > 0 && (!X || !labels))) HDB_THROW(HDB_EINVAL, "bad arguments");
+        if (n >= (int64_t)INT32_MAX) HDB_THROW(HDB_EINVAL, "validity: n must be below 2^31 (int32 ids)");
+        ValidityResult r;
+        {
+            Stager s(ctx);
+            const double *dX = s.in(X, (size_t)n * d);
+            const int32_t *dl = s.in(labels, (size_t)n);
+            double *dc = s.out(apts_core, (size_t)n);
+            int32_t *di = s.out(internal, (size_t)n);
+            validity_index_device(ctx, dX, n, d, dl, K, metric, splits, small_max, r, dc, di);
+            s.finish();
+        }
+        // the K-length results are host values: to the caller's memory, wherever it is
+        const auto put = [&](void *dst, const void *src, size_t bytes) {
+            if (!dst || !bytes) return;
+            if (is_device_ptr(dst))
+                HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+            else
+                std::memcpy(dst, src, bytes);
+        };
+        const size_t nk = (size_t)K;
+        put(validity, r.validity.data(), 8 * nk);
+        put(sparseness, r.sparseness.data(), 8 * nk);
+        put(separation, r.separation.data(), 8 * nk);
+        put(nearest_cluster, r.nearest.data(), 4 * nk);
+        put(size, r.size.data(), 4 * nk);
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));  // r dies with this call
+        *index = r.index;
+    });
+}
+
 int hdb_bubble_stats(hdb_ctx *ctx, const double *X, int64_t n, int32_t d, const int32_t *bubble_of, int64_t nb,
                      int32_t variant, double *ls, double *ss, double *rep, double *info) {
     return guarded(ctx, [&] {

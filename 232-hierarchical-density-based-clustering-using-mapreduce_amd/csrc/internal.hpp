@@ -111,6 +111,24 @@ void attach_points_device(hdb_ctx *ctx, const double *X, int64_t n, int d, const
                           int64_t m, int min_pts, int metric, int splits, double *core_q, int32_t *nearest,
                           double *level);
 void attach_stats_init(hdb_ctx *ctx);  // stat attach_last_splits
+// hdb_validity_index (validity.hip): the K-length results and the index are host values, entry c - 1
+// for label c
+struct ValidityResult {
+    double index = 0.0;
+    std::vector<double> validity, sparseness, separation;
+    std::vector<int32_t> nearest, size;
+};
+constexpr int32_t VALIDITY_SMALL_LIMIT = 2048;  // members the small-cluster Prim holds in LDS, at most
+// the DBCV index of a labelling; X, labels and the nullable n-length outputs on the device; splits:
+// candidate columns of both scans over grid.y (0: chosen); small_max: clusters up to this size share the
+// one Prim launch, larger ones go through boruvka_device (0: all of them); synchronises
+void validity_index_device(hdb_ctx *ctx, const double *X, int64_t n, int d, const int32_t *labels, int32_t K,
+                           int metric, int splits, int32_t small_max, ValidityResult &res, double *core_out,
+                           int32_t *internal_out);
+void validity_stats_init(hdb_ctx *ctx);  // stats validity_last_splits, validity_last_core_splits
+// its host epilogue (validity.cpp)
+void validity_cores_host(const double *totals, const int64_t *off, int32_t K, int d, double *cores);
+void validity_finish_host(ValidityResult &r, int64_t n);
 // K2b's infinite-weight tail on host arrays (inf_edges.cpp): X, core in id order; (ea, eb)[m] the
 // finite edges K2b found.  Writes the +inf edges that join their trees under (w, s, lo, hi) and
 // returns their count; rows_left / first_left: rows outside the largest tree that only NaN

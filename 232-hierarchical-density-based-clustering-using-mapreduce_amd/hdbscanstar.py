@@ -455,6 +455,44 @@ def approximate_predict(tree: ClusterTree, X, core, Q, minPts: int, distanceFunc
     return Prediction(lab, tl, nearest, level, core_q, sc)
 
 
+class Validity:
+    """The result of validity_index: ``index`` (the DBCV index, a float in [-1, 1]); per cluster
+    (entry c - 1 = label c) ``validity``, ``sparseness``, ``separation``, ``nearest_cluster`` (0:
+    none) and ``size``; per row ``core`` (the all-points core distance, 0 for noise) and
+    ``internal`` (1: an internal node of its cluster's tree)."""
+
+    def __init__(self, index, validity, sparseness, separation, nearest_cluster, size, core, internal):
+        self.index, self.validity, self.sparseness, self.separation = index, validity, sparseness, separation
+        self.nearest_cluster, self.size, self.core, self.internal = nearest_cluster, size, core, internal
+
+
+def validity_index(X, labels, distanceFunction=None, n_clusters=None, ctx=None, splits: int = 0,
+                   small_max: int | None = None) -> Validity:
+    """How good a labelling is: the DBCV validity index (Moulavi et al., SDM 2014) of ``labels``
+    (0 = noise, 1..n_clusters; n_clusters defaults to labels.max()) over the rows of X, under any
+    of the five metrics (hdb_validity_index; the contract is in include/hdbmi.h).  Higher is
+    better; compare the results of a sweep over minPts, minClSize, the metric or a level cut by
+    it.  numpy arrays or torch device tensors; the arrays of the result live where X does.
+    ``splits`` > 0 forces the candidate-column count of both scans and ``small_max`` the size up to
+    which clusters share the one Prim launch (0: every cluster through Boruvka); no bit of the
+    result depends on either."""
+    Xa, la = A.Arr(X, np.float64), A.Arr(labels, np.int32)
+    if Xa.obj.ndim != 2 or la.obj.shape[0] != Xa.obj.shape[0]:
+        raise ValueError("X must be n x d and labels must have one entry per row")
+    n, d = Xa.obj.shape
+    K = int(n_clusters) if n_clusters is not None else (int(la.obj.max()) if n else 0)
+    K = max(K, 0)
+    val, spa, sep = (A.new_like(Xa, (K,), np.float64) for _ in range(3))
+    near, size = A.new_like(Xa, (K,), np.int32), A.new_like(Xa, (K,), np.int32)
+    core, internal = A.new_like(Xa, (n,), np.float64), A.new_like(Xa, (n,), np.int32)
+    index = A.C.c_double()
+    c = A.context_for(ctx, Xa, la)
+    A.call("hdb_validity_index_route", c.h, Xa.p, n, d, la.p, K, metric_of(distanceFunction), int(splits),
+           1024 if small_max is None else int(small_max), A.C.byref(index), A.ptr(val), A.ptr(spa), A.ptr(sep),
+           A.ptr(near), A.ptr(size), A.ptr(core), A.ptr(internal), what="validity_index")
+    return Validity(index.value, val, spa, sep, near, size, core, internal)
+
+
 MUST_LINK, CANNOT_LINK = 0, 1  # HDB_CONSTRAINT_*
 
 

@@ -329,6 +329,77 @@ int hdb_attach_points_splits(hdb_ctx *ctx, const double *X, int64_t n, int32_t d
                              const double *Q, int64_t m, int32_t min_pts, int32_t metric, int32_t attach_splits,
                              double *core_q, int32_t *nearest, double *level);
 
+/* --------------------------------------------------------- validity of a labelling: the DBCV index
+ * Density-Based Clustering Validation (Moulavi, Jaskowiak, Campello, Zimek, Sander, SDM 2014) of a
+ * labelling of X, for all five metrics and every d >= 1.  The reference has no such routine: the
+ * contract is this library's own, one fixed operation order, bit-exact against a plain restatement
+ * (tests/validity_reference.py).
+ * Input: X (n x d), labels (n; 0 is noise, 1..K are clusters), K >= 0, metric.  A label outside
+ * 0..K is HDB_EINVAL and the message names the first offending row.  Rows labelled 0 are never read
+ * as coordinates (a NaN there is accepted).  A non-finite coordinate in a labelled row is HDB_EINVAL
+ * with "non-finite input" and the first such row.  The context stays usable after either.
+ *   dist(i, j)   DistanceCalculator.computeDistance(X[i], X[j]), i < j: the bits of
+ *                hdb_distance_rows.  No contraction.
+ *   members      of cluster c: its rows in ascending id; n_c their count.
+ *   1. all-points core distance of a member x of c: over the other members y of c with
+ *      dist(x, y) > 0 (self -- also skipped by index --, duplicates, slightly negative cosine and
+ *      Pearson values and NaN contribute nothing), t = 1.0 / dist and p = t^d by right-to-left binary
+ *      exponentiation (r = 1; b = t; e = d; while e: if e & 1: r = r * b; e >>= 1; if e: b = b * b).
+ *      Summation shape: the members are cut into blocks of HDB_VALIDITY_SUM_BLOCK consecutive
+ *      members by position in the member order; a block's partial starts at 0.0 and adds its
+ *      contributing p in member order; the total starts at 0.0 and adds the block partials in block
+ *      order.  apts_core[x] = total == 0 ? 0.0 : pow(total / (double)(n_c - 1), -1.0 / d), the host
+ *      libm's pow, applied on the host to the n totals for device and host pointers alike (the call
+ *      synchronises).  n_c == 1 and noise rows: 0.0.  An overflow of p or of the total to +inf gives
+ *      the core 0.0, as computed: at large d (or tiny distances) the index inherits DBCV's known
+ *      range problem.
+ *   2. MST of c: the tree hdb_mst_boruvka returns for the members' rows, in member order, with these
+ *      cores -- the unique MST under the strict order (w, s, lo, hi).  A status it returns
+ *      propagates, with the cluster label added to the message (cosine with an all-zero member row:
+ *      only NaN pairs reach it, "non-finite input").
+ *   3. deg = the degree in that tree; internal members have deg >= 2, internal edges are the tree
+ *      edges with both ends internal.  If c has no internal edge (n_c <= 3, stars), every member is
+ *      internal and every tree edge is internal.  sparseness[c] = the largest internal edge weight;
+ *      0.0 for n_c <= 1.
+ *   4. for internal x in c and internal y in c' != c: w(x, y) = dist, replaced by apts_core[x], then
+ *      by apts_core[y], on a strict '>' only; a pair whose w is NaN is no candidate.  separation[c] =
+ *      the minimum of w over all such pairs, nearest_cluster[c] = the smallest label c' that attains
+ *      it; with no such pair (c empty, no other non-empty cluster): +inf and 0.
+ *   5. validity[c] = (separation - sparseness) / max(separation, sparseness); 0.0 when that max is
+ *      0, when c is empty, or when separation is +inf.
+ *   6. index = the sum, in ascending label order from 0.0, of ((double)n_c / (double)n) *
+ *      validity[c]; n includes noise; computed on the host.  n == 0 or K == 0: HDB_OK, index 0.0.
+ * Outputs: index (a host double, required); each of the others may be NULL on its own: validity,
+ * sparseness, separation (K doubles each), nearest_cluster, size (K int32 each; entry c - 1 is
+ * label c), apts_core (n doubles), internal (n int32: 0 or 1, 0 for noise).  Pointer rules as
+ * hdb_knn: host or device per pointer; ctx is required.  n >= 2^31: HDB_EINVAL.
+ * Two tiled all-pairs FP64 scans in the style of the attach scan (kernel timers "validity_core",
+ * "validity_sep"); clusters of up to small_max members get their trees from one launch of a dense
+ * Prim, one workgroup per cluster ("validity_mst_small"), larger ones go one by one through
+ * hdb_mst_boruvka's device path under its own timers.
+ * hdb_validity_index_splits is the same call with the candidate-column count of both scans as an
+ * argument: splits = 0 chooses it, 1..65535 forces it, anything else is HDB_EINVAL; it changes no
+ * bit of any output.  In the core scan the columns fall on sum-block boundaries and every block's
+ * partial is stored (sum over c of n_c * ceil(n_c / HDB_VALIDITY_SUM_BLOCK) doubles); a chosen
+ * count drops to 1 when that store would exceed 2^22 doubles, a forced one is honoured.  Stats
+ * "validity_last_splits" (the separation scan) and "validity_last_core_splits" of the last call.
+ * hdb_validity_index_route adds small_max (0..2048; 0 sends every cluster through the Boruvka
+ * path), HDB_VALIDITY_SMALL_MAX in the other two; it changes no bit either.  Both are arguments of
+ * the call, not context options: nothing is left set. */
+#define HDB_VALIDITY_SUM_BLOCK 512
+#define HDB_VALIDITY_SMALL_MAX 1024
+int hdb_validity_index(hdb_ctx *ctx, const double *X, int64_t n, int32_t d, const int32_t *labels, int32_t K,
+                       int32_t metric, double *index, double *validity, double *sparseness, double *separation,
+                       int32_t *nearest_cluster, int32_t *size, double *apts_core, int32_t *internal);
+int hdb_validity_index_splits(hdb_ctx *ctx, const double *X, int64_t n, int32_t d, const int32_t *labels, int32_t K,
+                              int32_t metric, int32_t splits, double *index, double *validity, double *sparseness,
+                              double *separation, int32_t *nearest_cluster, int32_t *size, double *apts_core,
+                              int32_t *internal);
+int hdb_validity_index_route(hdb_ctx *ctx, const double *X, int64_t n, int32_t d, const int32_t *labels, int32_t K,
+                             int32_t metric, int32_t splits, int32_t small_max, double *index, double *validity,
+                             double *sparseness, double *separation, int32_t *nearest_cluster, int32_t *size,
+                             double *apts_core, int32_t *internal);
+
 /* --------------------------------------------------------- bubble statistics (a11, a12)
  * Bulk CombineStep (CombineStep.java:18-64) over a partition: member order = ascending
  * point index (D5).  Outputs per bubble: ls, ss, rep (nb*d), info (nb*3: extent, nnDist, n).
