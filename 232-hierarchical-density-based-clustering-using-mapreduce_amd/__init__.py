@@ -19,6 +19,6 @@ from .hdbscanstar import (CosineSimilarity, DistanceCalculator, EuclideanDistanc
                           ClusterTree, ConstrainedLabels, Prediction, approximate_predict, cluster_tree,
                           cluster_tree_bound, constrained_flat_labels, distance_rows, flat_labels,
                           labels_at_levels, outlier_ranking, outlier_scores, predict_labels,
-                          Validity, validity_index)
+                          Validity, validity_index, Membership, exemplars, membership_rows, membership_vectors)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

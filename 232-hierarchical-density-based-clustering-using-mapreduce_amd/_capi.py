@@ -104,6 +104,10 @@ SIGNATURES = {
                                      _vp, _vp, _vp, _vp]),
     "hdb_labels_at_levels": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _vp]),
     "hdb_predict_labels": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "hdb_exemplars": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "hdb_exemplar_distances": (_int, [_vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp]),
+    "hdb_exemplar_distances_splits": (_int, [_vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp]),
+    "hdb_membership_vectors": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "hdb_constrained_flat_labels": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
                                            _vp, _vp, _vp]),
     "hdb_local_mst_ids": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),

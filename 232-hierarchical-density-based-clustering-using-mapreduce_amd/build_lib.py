@@ -16,9 +16,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.environ.get("HDBMI_OUT") or os.path.join(HERE, "lib")
 LIB = os.path.join(OUT, "libhdbmi.so")
-SOURCES = ["context.cpp", "options.cpp", "capi.cpp", "local_model.cpp", "flat.cpp", "constraints.cpp", "formats.cpp", "inf_edges.cpp", "validity.cpp", "knn.hip", "nearest.hip", "prim.hip",
-           "bubbles.hip", "merge.hip", "spatial.hip", "boruvka_generic.hip", "attach.hip", "validity.hip", "knn_mfma.hip", "flat.hip", "constraints.hip", "comm.cpp"] + [f"knn_d{d}.hip" for d in (1, 2, 3, 4, 5, 6, 8, 16)]
-HEADERS = ["common.hpp", "internal.hpp", "knn_impl.hpp", "sort.hpp", "ssort.hpp"]
+SOURCES = ["context.cpp", "options.cpp", "capi.cpp", "local_model.cpp", "flat.cpp", "constraints.cpp", "formats.cpp", "inf_edges.cpp", "validity.cpp", "soft.cpp", "knn.hip", "nearest.hip", "prim.hip",
+           "bubbles.hip", "merge.hip", "spatial.hip", "boruvka_generic.hip", "attach.hip", "validity.hip", "soft.hip", "knn_mfma.hip", "flat.hip", "constraints.hip", "comm.cpp"] + [f"knn_d{d}.hip" for d in (1, 2, 3, 4, 5, 6, 8, 16)]
+HEADERS = ["common.hpp", "internal.hpp", "attach_scan.hpp", "knn_impl.hpp", "sort.hpp", "ssort.hpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 # -ffp-contract=off: the reference (Java) never fuses a*b+c; bit-exact parity needs the same.

@@ -706,6 +706,94 @@ int hdb_predict_labels(hdb_ctx *ctx, const int32_t *parent, const double *birth,
         });
 }
 
+int hdb_exemplars(hdb_ctx *ctx, const int32_t *parent, const int32_t *flat_label, int64_t K, int64_t C,
+                  const int32_t *point_cluster, const double *point_level, int64_t n, int32_t *ids,
+                  int64_t *offsets, int64_t *n_exemplars) {
+    const bool bad = K < 0 || C < 0 || n < 0 || !offsets || (K > 0 && (!parent || !flat_label)) ||
+                     (n > 0 && (!point_cluster || !point_level || !ids));
+    return host_or_device(
+        ctx, bad,
+        [&] {  // the selection is host work: device arrays come down, the results go back up
+            const auto hp = to_host(ctx, parent, (size_t)K), hf = to_host(ctx, flat_label, (size_t)K);
+            const auto hc = to_host(ctx, point_cluster, (size_t)n);
+            const auto hl = to_host(ctx, point_level, (size_t)n);
+            std::vector<int32_t> hi((size_t)n);
+            std::vector<int64_t> ho((size_t)C + 1);
+            const int64_t E = exemplars_host(hp.data(), hf.data(), K, C, hc.data(), hl.data(), n, hi.data(), ho.data());
+            const auto put = [&](void *dst, const void *src, size_t bytes) {
+                if (!bytes) return;
+                if (is_device_ptr(dst))
+                    HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+                else
+                    std::memcpy(dst, src, bytes);
+            };
+            put(ids, hi.data(), sizeof(int32_t) * (size_t)E);
+            put(offsets, ho.data(), sizeof(int64_t) * ((size_t)C + 1));
+            HIP_CHECK(hipStreamSynchronize(ctx->stream));  // the host copies die with this call
+            if (n_exemplars) *n_exemplars = E;
+        },
+        [&] {
+            std::vector<int64_t> ho((size_t)C + 1);  // nothing is written when the input is refused
+            std::vector<int32_t> hi((size_t)n);
+            const int64_t E = exemplars_host(parent, flat_label, K, C, point_cluster, point_level, n, hi.data(), ho.data());
+            std::copy(hi.begin(), hi.begin() + E, ids);
+            std::copy(ho.begin(), ho.end(), offsets);
+            if (n_exemplars) *n_exemplars = E;
+            return HDB_OK;
+        });
+}
+
+int hdb_exemplar_distances(hdb_ctx *ctx, const double *X, int64_t n, int32_t d, const int32_t *ids, int64_t n_ids,
+                           const int64_t *offsets, int64_t C, const double *Q, int64_t m, int32_t metric,
+                           double *dmin) {
+    return hdb_exemplar_distances_splits(ctx, X, n, d, ids, n_ids, offsets, C, Q, m, metric, 0, dmin);
+}
+
+int hdb_exemplar_distances_splits(hdb_ctx *ctx, const double *X, int64_t n, int32_t d, const int32_t *ids,
+                                  int64_t n_ids, const int64_t *offsets, int64_t C, const double *Q, int64_t m,
+                                  int32_t metric, int32_t splits, double *dmin) {
+    return guarded(ctx, [&] {
+        check_metric(metric);
+        if (splits < 0 || splits > 65535) HDB_THROW(HDB_EINVAL, "exemplar distances: splits must be in 0..65535");
+        if (n < 0 || m < 0 || d <= 0 || n_ids < 0 || C < 0 || !offsets || (n > 0 && !X) || (n_ids > 0 && !ids) ||
+            (m > 0 && !Q) || (m > 0 && C > 0 && !dmin))
+            HDB_THROW(HDB_EINVAL, "bad arguments");
+        Stager s(ctx);
+        const double *dX = s.in(X, (size_t)n * d), *dQ = s.in(Q, (size_t)m * d);
+        const int32_t *di = s.in(ids, (size_t)n_ids);
+        const int64_t *dof = s.in(offsets, (size_t)C + 1);
+        double *dd = s.out(dmin, (size_t)m * (size_t)C);
+        exemplar_distances_device(ctx, dX, n, d, di, n_ids, dof, C, dQ, m, metric, splits, dd);
+        s.finish();
+    });
+}
+
+int hdb_membership_vectors(hdb_ctx *ctx, const int32_t *parent, const double *birth, const double *death,
+                           const int32_t *flat_label, int64_t K, int64_t C, const int32_t *anchor,
+                           const double *level, const double *dmin, int64_t m, double *vectors, double *prob,
+                           int32_t *labels) {
+    const bool bad = K < 0 || C < 0 || m < 0 || (K > 0 && (!parent || !birth || !death || !flat_label)) ||
+                     (m > 0 && (!anchor || !level)) || (m > 0 && C > 0 && (!dmin || !vectors));
+    return host_or_device(
+        ctx, bad,
+        [&] {
+            if (m == 0) return;
+            Stager sg(ctx);
+            const size_t nk = (size_t)K, nm = (size_t)m, nmc = (size_t)m * (size_t)C;
+            const int32_t *dp = sg.in(parent, nk), *dfl = sg.in(flat_label, nk), *da = sg.in(anchor, nm);
+            const double *db = sg.in(birth, nk), *dd = sg.in(death, nk), *dlv = sg.in(level, nm);
+            const double *ddm = sg.in(dmin, nmc);
+            double *dv = sg.out(vectors, nmc), *dpr = sg.out(prob, nm);
+            int32_t *dlab = sg.out(labels, nm);
+            membership_vectors_device(ctx, dp, db, dd, dfl, K, C, da, dlv, ddm, m, dv, dpr, dlab);
+            sg.finish();
+        },
+        [&] {
+            return membership_vectors_host(parent, birth, death, flat_label, K, C, anchor, level, dmin, m, vectors, prob,
+                                           labels);
+        });
+}
+
 int hdb_constrained_flat_labels(hdb_ctx *ctx, const int32_t *parent, const double *stability, const int32_t *min_id,
                                 int64_t K, const int32_t *point_cluster, int64_t n, const int32_t *ca,
                                 const int32_t *cb, const int32_t *ctype, int64_t m, int32_t *num_sat,

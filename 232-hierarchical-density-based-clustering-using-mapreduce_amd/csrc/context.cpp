@@ -243,6 +243,7 @@ int hdb_ctx_create(int device, hdb_ctx **out) {
         boruvka_generic_stats_init(c);
         attach_stats_init(c);
         validity_stats_init(c);
+        soft_stats_init(c);
         // per-kernel HIP-event timing from birth (contexts created on worker threads, bench.py)
         if (const char *e = getenv("HDB_KERNEL_TIMING")) c->timing = atoi(e) != 0;
         // A/B runs of unmodified programs: HDB_OPTS="name=value,name=value", every pair applied

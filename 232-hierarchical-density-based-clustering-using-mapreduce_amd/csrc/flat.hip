@@ -2525,4 +2525,27 @@ void predict_labels_device(hdb_ctx *ctx, const int32_t *parent, const double *bi
     if (e & PE_LEVEL) HDB_THROW(HDB_EINVAL, "predict labels: NaN level");
 }
 
+// The tables of sections 8 and 9 for a caller outside this file (soft.hip), built by the same
+// kernels into the caller's scratch: anc (J rows of K + 1), bt, em (ord_enc keys) and the flat label
+// of the nearest selected cluster, whose final buffer (near_a or near_b) is returned.  A parent
+// label out of range sets bit TREE_TABLES_BAD_PARENT of *err.  Stream-ordered.
+static_assert(TREE_TABLES_BAD_PARENT == LE_PARENT, "one bit for one error");
+const int32_t *tree_tables_device(hdb_ctx *ctx, const int32_t *parent, const double *birth, const double *death,
+                                  const int32_t *flat_label, int32_t K, int J, int32_t *anc, double *bt,
+                                  unsigned long long *em, int32_t *near_a, int32_t *near_b, int *err) {
+    hipStream_t st = ctx->stream;
+    const int64_t stride = (int64_t)K + 1;
+    const int gk = grid_for(stride);
+    hipLaunchKernelGGL(lc_init, dim3(gk), dim3(256), 0, st, parent, birth, K, anc, bt, err);
+    for (int j = 1; j < J; j++)
+        hipLaunchKernelGGL(lc_double, dim3(gk), dim3(256), 0, st, anc + (j - 1) * stride, anc + j * stride, K);
+    hipLaunchKernelGGL(pr_init, dim3(gk), dim3(256), 0, st, death, flat_label, K, em, near_a);
+    for (int j = 0; j < J; j++) {
+        hipLaunchKernelGGL(pr_double, dim3(gk), dim3(256), 0, st, anc + j * stride, K, em, near_a, near_b);
+        std::swap(near_a, near_b);
+    }
+    HIP_CHECK(hipGetLastError());
+    return near_a;
+}
+
 }  // namespace hdb

@@ -129,6 +129,33 @@ void validity_stats_init(hdb_ctx *ctx);  // stats validity_last_splits, validity
 // its host epilogue (validity.cpp)
 void validity_cores_host(const double *totals, const int64_t *off, int32_t K, int d, double *cores);
 void validity_finish_host(ValidityResult &r, int64_t n);
+// soft clustering (soft.hip, soft.cpp; include/hdbmi.h "soft clustering")
+// the exemplar-distance scan: dmin (m x C) = per query row and segment of ids the smallest
+// dist(Q[i], X[ids[e]]); every array on the device; ids and offsets are validated on the device
+// (one word read back) before anything is written; splits: candidate columns over grid.y (0: chosen)
+void exemplar_distances_device(hdb_ctx *ctx, const double *X, int64_t n, int d, const int32_t *ids, int64_t E,
+                               const int64_t *offsets, int64_t C, const double *Q, int64_t m, int metric, int splits,
+                               double *dmin);
+void soft_stats_init(hdb_ctx *ctx);  // stat soft_last_splits
+// hdb_membership_vectors with every array on the device (prob, labels nullable); synchronises
+void membership_vectors_device(hdb_ctx *ctx, const int32_t *parent, const double *birth, const double *death,
+                               const int32_t *flat_label, int64_t K, int64_t C, const int32_t *anchor,
+                               const double *level, const double *dmin, int64_t m, double *vectors, double *prob,
+                               int32_t *labels);
+// the same on host arrays, and the exemplar selection (host only): returns the exemplar count
+int membership_vectors_host(const int32_t *parent, const double *birth, const double *death,
+                            const int32_t *flat_label, int64_t K, int64_t C, const int32_t *anchor,
+                            const double *level, const double *dmin, int64_t m, double *vectors, double *prob,
+                            int32_t *labels);
+int64_t exemplars_host(const int32_t *parent, const int32_t *flat_label, int64_t K, int64_t C,
+                       const int32_t *point_cluster, const double *point_level, int64_t n, int32_t *ids,
+                       int64_t *offsets);
+// the ancestor, birth, eps_max and nearest-selected tables of the level cut and the out-of-sample
+// labels (flat.hip sections 8 and 9) in the caller's scratch; returns the final nearest-selected buffer
+constexpr int TREE_TABLES_BAD_PARENT = 1;
+const int32_t *tree_tables_device(hdb_ctx *ctx, const int32_t *parent, const double *birth, const double *death,
+                                  const int32_t *flat_label, int32_t K, int J, int32_t *anc, double *bt,
+                                  unsigned long long *em, int32_t *near_a, int32_t *near_b, int *err);
 // K2b's infinite-weight tail on host arrays (inf_edges.cpp): X, core in id order; (ea, eb)[m] the
 // finite edges K2b found.  Writes the +inf edges that join their trees under (w, s, lo, hi) and
 // returns their count; rows_left / first_left: rows outside the largest tree that only NaN

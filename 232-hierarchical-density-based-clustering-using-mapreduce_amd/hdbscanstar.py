@@ -241,6 +241,32 @@ class HDBSCANStar:
                int(attach_splits), A.ptr(core_q), A.ptr(nearest), A.ptr(level), what="attachPoints")
         return core_q, nearest, level
 
+    def exemplarDistances(self, dataSet, ids, offsets, queries, distanceFunction=None, splits: int = 0):
+        """The exemplar-distance scan of soft clustering (hdb_exemplar_distances): ``dmin`` (m x C)
+        with dmin[i][f - 1] = the smallest distance from row i of ``queries`` (the query row first)
+        to the rows ``dataSet[ids[e]]`` of segment f, offsets[f - 1] <= e < offsets[f]; +inf for an
+        empty segment, a NaN distance is no candidate.  ``ids`` / ``offsets`` as exemplars returns
+        them, or any arrays of that form (ids in 0..n-1, offsets ascending from 0 to len(ids)).  Each
+        array may be host or device memory; the result lives where ``queries`` does.  ``splits`` > 0
+        forces the number of candidate columns the scan merges (no bit of the result depends on it).
+        Memory: the output is m * C doubles; scratch beyond it is the gathered and packed exemplar
+        rows, the packed queries and splits * m * C partial minima -- chunk ``queries`` when that is
+        too much."""
+        X, Q = A.Arr(dataSet, np.float64), A.Arr(queries, np.float64)
+        ia, oa = A.Arr(ids, np.int32), A.Arr(offsets, np.int64)
+        n, d = X.obj.shape
+        m = Q.obj.shape[0]
+        if Q.obj.ndim != 2 or Q.obj.shape[1] != d:
+            raise ValueError("queries must be m x d with the training rows' d")
+        if oa.obj.ndim != 1 or oa.obj.shape[0] < 1 or ia.obj.ndim != 1:
+            raise ValueError("offsets needs C + 1 entries, ids one per exemplar")
+        C = int(oa.obj.shape[0]) - 1
+        dmin = A.new_like(Q, (m, C), np.float64)
+        c = A.context_for(self.ctx, Q, X, ia, oa)
+        A.call("hdb_exemplar_distances_splits", c.h, X.p, n, d, ia.p, int(ia.obj.shape[0]), oa.p, C, Q.p, m,
+               metric_of(distanceFunction), int(splits), A.ptr(dmin), what="exemplarDistances")
+        return dmin
+
 
 def flat_labels(va, vb, w, n: int, minClSize: int, ctx=None):
     """Global HDBSCAN* flat partition over a merged MST (the reference's
@@ -453,6 +479,93 @@ def approximate_predict(tree: ClusterTree, X, core, Q, minPts: int, distanceFunc
     core_q, nearest, level = HDBSCANStar(ctx).attachPoints(X, core, Q, minPts, distanceFunction)
     tl, lab, sc = predict_labels(tree, nearest, level, flat_label, ctx=ctx)
     return Prediction(lab, tl, nearest, level, core_q, sc)
+
+
+def _selection(tree: ClusterTree, flat_label):
+    """(flat_label array, C): the tree's own selection, or the given one with C = its maximum"""
+    if flat_label is None:
+        return tree.flat_label, tree.n_clusters
+    fl = A.Arr(flat_label, np.int32)
+    return fl.obj, (max(int(fl.obj.max()), 0) if fl.obj.shape[0] else 0)
+
+
+def exemplars(tree: ClusterTree, flat_label=None, ctx=None):
+    """The exemplars of the selected clusters (hdb_exemplars): the points that leave a leaf of the
+    cluster tree at the leaf's smallest point level, each under the flat label of the nearest
+    selected cluster above its leaf (``flat_label`` per cluster: the tree's own by default, or the
+    one constrained_flat_labels returns).  Returns (ids, offsets): int32 point ids ordered by (flat
+    label, id) and int64 offsets with the ids of flat label f at offsets[f - 1]:offsets[f].  The
+    arrays live where the tree's points do; host arrays without a ctx need no device."""
+    fl_obj, C = _selection(tree, flat_label)
+    par, fl = A.Arr(tree.parent, np.int32), A.Arr(fl_obj, np.int32)
+    pc, pl = A.Arr(tree.point_cluster, np.int32), A.Arr(tree.point_level, np.float64)
+    K, n = int(par.obj.shape[0]), int(pc.obj.shape[0])
+    if fl.obj.shape[0] != K:
+        raise ValueError("flat_label needs one entry per cluster")
+    ids, offsets = A.new_like(pc, (n,), np.int32), A.new_like(pc, (C + 1,), np.int64)
+    E = np.zeros(1, np.int64)
+    c = A.context_for(ctx, pc, par, fl, host_ok=True)
+    A.call("hdb_exemplars", c.h if c else None, par.p, fl.p, K, C, pc.p, pl.p, n, A.ptr(ids), A.ptr(offsets), A.ptr(E),
+           what="exemplars")
+    return ids[:int(E[0])], offsets
+
+
+class Membership:
+    """The result of membership_vectors, one row per query: ``vectors`` (m x C; entry f - 1 is the
+    membership in flat label f, the row sums to ``prob`` or is zero), ``prob`` (how strongly the
+    query belongs to any cluster), ``labels`` (the flat label of the row's first maximum, 0 for a
+    zero row) and ``dist`` (m x C, the distance to each cluster's nearest exemplar)."""
+
+    def __init__(self, vectors, prob, labels, dist):
+        self.vectors, self.prob, self.labels, self.dist = vectors, prob, labels, dist
+
+
+def membership_vectors(tree: ClusterTree, X, Q=None, core=None, minPts=None, distanceFunction=None, flat_label=None,
+                       ctx=None) -> Membership:
+    """Soft clustering (hdb_exemplars, hdb_exemplar_distances, hdb_membership_vectors; the
+    contract is in include/hdbmi.h): how strongly each row belongs to each selected cluster of the
+    fitted ``tree`` over the training rows X.  With ``Q`` None the rows are the training rows, each
+    anchored at its own (point_cluster, point_level); otherwise the rows of Q, attached through
+    approximate_predict (``core`` = the training rows' core distances and ``minPts`` as there).
+    Tensors in give tensors out; the results live where the queries do.  The distance scan needs a
+    device.  Memory: ``dist`` and ``vectors`` are m x C doubles each -- chunk the queries when that
+    is too much."""
+    ids, offsets = exemplars(tree, flat_label, ctx=ctx)
+    if Q is None:
+        queries, anchor, level = X, tree.point_cluster, tree.point_level
+    else:
+        if core is None or minPts is None:
+            raise ValueError("new rows need the training rows' core distances and minPts")
+        queries = Q
+        pred = approximate_predict(tree, X, core, Q, minPts, distanceFunction, flat_label, ctx=ctx)
+        anchor = pred.tree_labels
+        if A.is_torch(pred.level):
+            import torch
+            pl = tree._t("point_level").to(pred.level.device)[pred.nearest.to(torch.int64).clamp(min=0)]
+            level = torch.where(pl > pred.level, pl, pred.level)
+        else:
+            pl = np.asarray(tree.host().point_level)[np.maximum(pred.nearest, 0)] if tree.n else pred.level
+            level = np.where(pl > pred.level, pl, pred.level)
+    dist = HDBSCANStar(ctx).exemplarDistances(X, ids, offsets, queries, distanceFunction)
+    return membership_rows(tree, anchor, level, dist, flat_label, ctx=ctx)
+
+
+def membership_rows(tree: ClusterTree, anchor, level, dist, flat_label=None, ctx=None) -> Membership:
+    """hdb_membership_vectors on its own: the membership of queries given as anchor clusters (tree
+    labels, 0 = none), levels and their rows of exemplar distances (m x C).  Results live where
+    ``dist`` does; host arrays without a ctx run on the host with no device."""
+    fl_obj, C = _selection(tree, flat_label)
+    par, bi, de = A.Arr(tree.parent, np.int32), A.Arr(tree.birth, np.float64), A.Arr(tree.death, np.float64)
+    fl, an, lv, dm = A.Arr(fl_obj, np.int32), A.Arr(anchor, np.int32), A.Arr(level, np.float64), A.Arr(dist, np.float64)
+    K, m = int(par.obj.shape[0]), int(an.obj.shape[0])
+    if lv.obj.shape[0] != m or tuple(dm.obj.shape) != (m, C):
+        raise ValueError("one anchor, one level and one row of C distances per query")
+    vec = A.new_like(dm, (m, C), np.float64)
+    prob, lab = A.new_like(dm, (m,), np.float64), A.new_like(dm, (m,), np.int32)
+    c = A.context_for(ctx, dm, an, lv, par, fl, host_ok=True)
+    A.call("hdb_membership_vectors", c.h if c else None, par.p, bi.p, de.p, fl.p, K, C, an.p, lv.p, dm.p, m, A.ptr(vec),
+           A.ptr(prob), A.ptr(lab), what="membership_vectors")
+    return Membership(vec, prob, lab, dist)
 
 
 class Validity:

@@ -650,6 +650,95 @@ int hdb_predict_labels(hdb_ctx *ctx, const int32_t *parent, const double *birth,
                        const double *point_level, int64_t n, const int32_t *nearest, const double *level,
                        int64_t m, int32_t *tree_label, int32_t *labels, double *scores);
 
+/* ---------------------------------------------------------------- soft clustering
+ * Exemplars, exemplar distances and membership vectors: how strongly a point -- a training point or
+ * a new row -- belongs to each selected cluster.  The reference has no such routine: the contract is
+ * this library's own, restated in plain numpy over oracle distances (tests/soft_reference.py), and
+ * every comparison is bit-exact.
+ * Levels are distances: smaller means denser.  The arithmetic is FP64 with no contraction (no FMA).
+ * Every sum over clusters runs in ascending flat label.  Where a host and a device path exist they
+ * give the same bits.  Results that are NaN (they need negative, NaN or non-finite levels, or NaN
+ * entries in dmin) are out of scope: the value is whatever the arithmetic gives.
+ * Inputs are the arrays of hdb_flat_cluster_tree (K clusters; entry i describes tree label i + 1)
+ * plus a selection flat_label (K) with values 0..C: the tree's own, or the one
+ * hdb_constrained_flat_labels returns; C is the caller's count of selected clusters.  The selected
+ * cluster c_f of flat label f is the lowest tree label that carries f; an f that no cluster carries
+ * is an empty cluster (no exemplar, tree part 0).  The tree is validated with the rules of
+ * hdb_labels_at_levels and never trusted: parent[0] != 0, parent[i] outside 0..i, point_cluster
+ * outside 1..K, and a flat_label outside 0..C, give HDB_EINVAL and nothing has been written; there
+ * is no out-of-bounds read on host or device.
+ *
+ * 1. Exemplars: hdb_exemplars.
+ *   A tree cluster is a leaf when no cluster names it as parent.  Point x is an exemplar when
+ *   point_cluster[x] is a leaf and point_level[x] equals (== on doubles, -0.0 == 0.0) the smallest
+ *   point_level, under '<' from +inf, among the points with that point_cluster; a NaN level is
+ *   neither.  Its cluster is f(x), the flat_label of the nearest selected cluster on the path from
+ *   point_cluster[x] to the root, the leaf included; exemplars with f(x) = 0 are dropped.
+ *   ids (int32, room for n entries; the first offsets[C] are written) lists the exemplars ordered by
+ *   (f, id); offsets (int64, C + 1) has the segment of flat label f at offsets[f - 1] ..
+ *   offsets[f].  *n_exemplars (host, nullable) receives offsets[C].  A selected cluster without an
+ *   exemplar cannot arise from a real tree, but the format allows an empty segment.  The selection
+ *   itself is host work, O(n + K): device arrays are copied down and the result up; ctx may be NULL
+ *   when every pointer is host memory.  Synchronises.
+ *
+ * 2. Exemplar distances: hdb_exemplar_distances (device only, like hdb_attach_points).
+ *   dist(i, e) = DistanceCalculator.computeDistance(Q[i], X[ids[e]]), the query row first, in the
+ *   operation order of hdb_attach_points: the bits of hdb_distance_rows.  All five metrics, every
+ *   d >= 1.  dmin (m x C, row-major, 64-bit indexing): dmin[i][f - 1] = the minimum over the
+ *   exemplars e of segment f under numeric '<'; a NaN distance is never a candidate; a -0.0 result is
+ *   stored as +0.0; +inf when the segment is empty or every distance is NaN.
+ *   ids (n_ids) and offsets (C + 1) are arbitrary caller arrays: an id outside 0..n-1, offsets[0]
+ *   != 0, a descending pair, or offsets[C] != n_ids give HDB_EINVAL and dmin has not been written.
+ *   m == 0 or C == 0: HDB_OK.  Pointer rules as hdb_knn.  Kernel timers "soft_scan", "soft_merge".
+ *   The candidate tiles are split over workgroup columns when m alone gives too few workgroups, and a
+ *   second kernel merges the columns' minima; the minimum is exact and commutative, so the count
+ *   changes no bit.  hdb_exemplar_distances_splits is the same call with that count as an
+ *   argument: 0 chooses it (what hdb_exemplar_distances does), 1..65535 forces it, anything else is
+ *   HDB_EINVAL; stat "soft_last_splits" = the count of the last call.
+ *   Memory: the output is m * C doubles.  Scratch beyond it is the gathered exemplar rows
+ *   (n_ids * d doubles), their packed copy and the packed queries (rows padded to a multiple of 8
+ *   columns) and, with more than one column, splits * m * C doubles of partial minima (a chosen
+ *   count keeps these within 2^25 doubles).  The caller chunks Q when that is too much.
+ *
+ * 3. Membership vectors: hdb_membership_vectors.
+ *   Query i is described by an anchor cluster a = anchor[i] (a tree label 1..K, or 0 for "no
+ *   anchor"; anything else is HDB_EINVAL), a level l = level[i] and its row of dmin (m x C).
+ *   A training point uses (point_cluster, point_level); a new row uses the tree_label of
+ *   hdb_predict_labels and max(level, point_level[nearest]) of hdb_attach_points, anchor 0 when
+ *   nearest is -1.
+ *   Merge level: with A = LCA(a, c) in the tree, B(c) = birth of A's child on the path to c when A
+ *     is a proper ancestor of c (c's own root when a forest leaves them without a common
+ *     ancestor), B(c) = -inf when a == c or a lies in c's subtree; M = B(c) > l ? B(c) : l.
+ *   Tree part: t[f] = M == 0 ? 1.0 : eps_max(c_f) / M with M taken for c = c_f; eps_max as in
+ *     hdb_predict_labels (the subtree minimum of death; the root: its descendants only).  For
+ *     finite non-negative levels t lies in [0, 1].
+ *   Probability: prob = min(1.0, max over f of t[f]), the maximum taken from 0.0 under '>'.
+ *   Distance part: Z = { f : dmin[f] <= 0 }.  Z non-empty: dv[f] = 1.0 / |Z| on Z, 0 elsewhere.
+ *     Else r[f] = 1.0 / dmin[f] (0 for +inf), S = the sum of r in ascending f, dv[f] = r[f] / S,
+ *     all 0 when S == 0.
+ *   Result: p[f] = dv[f] * t[f], P = the sum of p in ascending f,
+ *     vectors[i][f - 1] = P == 0 ? 0.0 : prob * (p[f] / P).  a == 0: a row of zeros and prob 0.
+ *   labels[i] = the first f whose entry exceeds ('>') every entry before it and 0.0, i.e. 1 + the
+ *     index of the row's first maximum, or 0 when the whole row is zero.
+ *   vectors (m x C) is required when m * C > 0; prob (m) and labels (m) are nullable.  m == 0:
+ *   HDB_OK.  Pointer rules as hdb_labels_at_levels: host, device or mixed, ctx may be NULL when
+ *   every pointer is host memory.  The device finds every LCA by binary lifting over the level
+ *   cut's ancestor tables, O(log K) per (query, cluster); kernel timer "soft_membership".
+ *   Synchronises. */
+int hdb_exemplars(hdb_ctx *ctx, const int32_t *parent, const int32_t *flat_label, int64_t K, int64_t C,
+                  const int32_t *point_cluster, const double *point_level, int64_t n, int32_t *ids,
+                  int64_t *offsets, int64_t *n_exemplars);
+int hdb_exemplar_distances(hdb_ctx *ctx, const double *X, int64_t n, int32_t d, const int32_t *ids, int64_t n_ids,
+                           const int64_t *offsets, int64_t C, const double *Q, int64_t m, int32_t metric,
+                           double *dmin);
+int hdb_exemplar_distances_splits(hdb_ctx *ctx, const double *X, int64_t n, int32_t d, const int32_t *ids,
+                                  int64_t n_ids, const int64_t *offsets, int64_t C, const double *Q, int64_t m,
+                                  int32_t metric, int32_t splits, double *dmin);
+int hdb_membership_vectors(hdb_ctx *ctx, const int32_t *parent, const double *birth, const double *death,
+                           const int32_t *flat_label, int64_t K, int64_t C, const int32_t *anchor,
+                           const double *level, const double *dmin, int64_t m, double *vectors, double *prob,
+                           int32_t *labels);
+
 /* Semi-supervised flat extraction (Main.java:49,434-436 "constraints=<file>"; Constraint.java,
  * HDBSCANStar.calculateNumConstraintsSatisfied :738-789, the constraint branches of
  * Cluster.propagate :98-142, findProminentClusters) from the arrays of hdb_flat_cluster_tree:
