@@ -709,6 +709,8 @@ int hdb_predict_labels(hdb_ctx *ctx, const int32_t *parent, const double *birth,
  *   Merge level: with A = LCA(a, c) in the tree, B(c) = birth of A's child on the path to c when A
  *     is a proper ancestor of c (c's own root when a forest leaves them without a common
  *     ancestor), B(c) = -inf when a == c or a lies in c's subtree; M = B(c) > l ? B(c) : l.
+ *     A root's birth is NaN (hdb_flat_cluster_tree), the further roots of a forest included: as
+ *     B(c) it fails the comparison, so M = l, as for -inf.
  *   Tree part: t[f] = M == 0 ? 1.0 : eps_max(c_f) / M with M taken for c = c_f; eps_max as in
  *     hdb_predict_labels (the subtree minimum of death; the root: its descendants only).  For
  *     finite non-negative levels t lies in [0, 1].
