@@ -35,6 +35,7 @@
 //  7. hdb_labels_at_levels cuts such a tree at arbitrary levels: ancestor tables by binary
 //     lifting, one thread per point over the sorted levels (section 8).
 #include <rocprim/device/device_scan.hpp>
+#include <rocprim/device/device_scan_by_key.hpp>
 
 #include <algorithm>
 #include <chrono>
@@ -50,7 +51,12 @@ namespace hdb {
 namespace {
 
 constexpr int32_t NONE = INT32_MAX;
-enum : int { FE_RANGE = 1, FE_NAN = 2, FE_CYCLE = 4, FE_ISOLATED = 8, FE_ROOTS = 16, FE_JUMP = 32 };
+enum : int { FE_RANGE = 1, FE_NAN = 2, FE_CYCLE = 4, FE_ISOLATED = 8, FE_ROOTS = 16, FE_JUMP = 32, FE_PASS = 64 };
+// trees of this many edges or more build the Kruskal tree by alpha-edge contraction (section 2b).
+// Smaller ones run few global depths and are launch-bound, and 2b adds about 50 launches: K6 alone
+// on the bench's data is 5-10 % behind the plain path at 2^16, 2^17 and 2^18 edges
+// (profiles/k6_contract/threshold.log), so the constant sits at the top of its allowed range.
+constexpr int64_t FLAT_CONTRACT_MIN_M = int64_t(1) << 18;
 
 // ------------------------------------------------------------------------- union-find
 // Randomised linking: the root with the lower (priority, id) hooks under the higher one, so
@@ -257,9 +263,27 @@ struct DC {
     int32_t *esize;     // m: |C(e)|
     int32_t *eminid;    // m: smallest point id in C(e)
     const int32_t *orig;  // vertex label -> point id (nullptr: the label is the point id)
+    // weights of the contracted tree's second pass (section 2b; nullptr: a vertex label is one
+    // point, an edge adds none)
+    const int32_t *wv = nullptr, *mv = nullptr;  // n: points and smallest id of a vertex label
+    const int32_t *wl = nullptr, *ml = nullptr;  // m: of the chain between an edge and its parent
     int64_t n, m;         // n: vertex labels (contracted labels are n + root edge rank)
 };
 __device__ __forceinline__ int32_t vid(const DC &c, int32_t x) { return c.orig ? c.orig[x] : x; }
+// size and smallest id of label x: the only places the depth kernels read them
+__device__ __forceinline__ int32_t lab_size(const DC &c, int32_t x) {
+    if (x < c.n) return c.wv ? c.wv[x] : 1;
+    return c.esize[x - c.n];
+}
+__device__ __forceinline__ int32_t lab_min(const DC &c, int32_t x) {
+    if (x < c.n) return c.mv ? c.mv[x] : vid(c, x);
+    return c.eminid[x - c.n];
+}
+// second pass: the chain above L edge r joins r's component with it, so a component's totals
+// are the same at whatever depth they are taken (esize / eminid then include the root edge's
+// own chain; ka_write takes it out again)
+__device__ __forceinline__ int32_t edge_size(const DC &c, int64_t r) { return c.wl ? c.wl[r] : 0; }
+__device__ __forceinline__ int32_t edge_min(const DC &c, int64_t r) { return c.ml ? c.ml[r] : NONE; }
 
 __global__ void dc_init(DC c, int b, int j, int64_t nl) {
     HDB_GRID_STRIDE(i, nl) {
@@ -323,8 +347,8 @@ __global__ __launch_bounds__(TB) void dc_root(DC c, int b, int j, int64_t nl) {
             // added by its root edge in dc_link
             const int32_t x = c.hooked[r];
             c.hooked[r] = rep;  // dc_link reads the representative back instead of a second find
-            const int32_t sz = x < 0 ? 0 : (x < c.n ? 1 : c.esize[x - c.n]);
-            const int32_t mi = x < 0 ? NONE : (x < c.n ? vid(c, x) : c.eminid[x - c.n]);
+            const int32_t sz = (x < 0 ? 0 : lab_size(c, x)) + edge_size(c, r);
+            const int32_t mi = min(x < 0 ? NONE : lab_min(c, x), edge_min(c, r));
             uint32_t h = uf_prio(rep, 0) & (SLOTS - 1);
             while (true) {  // <= TB distinct keys in 2x slots: always finds one
                 int32_t k = atomicCAS(&skey[h], -1, rep);
@@ -384,8 +408,8 @@ __global__ __launch_bounds__(TB) void dc_root_multi(DC c, int b, int j, int64_t 
                 const int32_t rep = uf_find(c.lr, c.lab[2 * r]);
                 const int32_t x = c.hooked[r];
                 c.hooked[r] = rep;
-                const int32_t sz = x < 0 ? 0 : (x < c.n ? 1 : c.esize[x - c.n]);
-                const int32_t mi = x < 0 ? NONE : (x < c.n ? vid(c, x) : c.eminid[x - c.n]);
+                const int32_t sz = (x < 0 ? 0 : lab_size(c, x)) + edge_size(c, r);
+                const int32_t mi = min(x < 0 ? NONE : lab_min(c, x), edge_min(c, r));
                 uint32_t h = uf_prio(rep, 0) & (SLOTS - 1);
                 while (true) {  // the table is kept below SLOTS - TB keys before every batch
                     const int32_t k = atomicCAS(&skey[h], -1, rep);
@@ -423,8 +447,12 @@ __global__ void dc_root_direct(DC c, int b, int j, int64_t nl) {
         c.hooked[r] = rep;
         atomicMax(&c.lr[rep].rootedge, (int32_t)r);
         if (x >= 0) {
-            atomicAdd(&c.lr[rep].csize, x < c.n ? 1 : c.esize[x - c.n]);
-            atomicMin(&c.lr[rep].cmin, x < c.n ? vid(c, x) : c.eminid[x - c.n]);
+            atomicAdd(&c.lr[rep].csize, lab_size(c, x));
+            atomicMin(&c.lr[rep].cmin, lab_min(c, x));
+        }
+        if (c.wl) {
+            atomicAdd(&c.lr[rep].csize, c.wl[r]);
+            atomicMin(&c.lr[rep].cmin, c.ml[r]);
         }
     }
 }
@@ -437,8 +465,8 @@ __global__ void dc_link(DC c, int b, int j, int64_t nl) {
             const int32_t rep = c.hooked[r];
             const LRec q = c.lr[rep];
             if (q.rootedge == (int32_t)r) {
-                c.esize[r] = q.csize + (rep < c.n ? 1 : c.esize[rep - c.n]);
-                c.eminid[r] = min(q.cmin, rep < c.n ? vid(c, rep) : c.eminid[rep - c.n]);
+                c.esize[r] = q.csize + lab_size(c, rep);
+                c.eminid[r] = min(q.cmin, lab_min(c, rep));
             }
         }
         const int64_t u = r | (int64_t(1) << b);  // the U edge paired with this thread
@@ -490,8 +518,8 @@ __global__ __launch_bounds__(TB) void dc_link_multi(DC c, int b, int j, int64_t 
                     const int32_t rep = c.hooked[r];
                     const LRec q = c.lr[rep];
                     if (q.rootedge == (int32_t)r) {
-                        c.esize[r] = q.csize + (rep < c.n ? 1 : c.esize[rep - c.n]);
-                        c.eminid[r] = min(q.cmin, rep < c.n ? vid(c, rep) : c.eminid[rep - c.n]);
+                        c.esize[r] = q.csize + lab_size(c, rep);
+                        c.eminid[r] = min(q.cmin, lab_min(c, rep));
                     }
                 }
                 const int64_t u = r | (int64_t(1) << b);
@@ -606,8 +634,8 @@ __global__ __launch_bounds__(TB) void dc_mid(DC c, int J, int LM, int LB, int *_
                     const int32_t rep = uf_find(c.lr, c.lab[2 * r]);
                     const int32_t x = c.hooked[r];
                     c.hooked[r] = rep;
-                    const int32_t sz = x < 0 ? 0 : (x < c.n ? 1 : c.esize[x - c.n]);
-                    const int32_t mi = x < 0 ? NONE : (x < c.n ? vid(c, x) : c.eminid[x - c.n]);
+                    const int32_t sz = (x < 0 ? 0 : lab_size(c, x)) + edge_size(c, r);
+                    const int32_t mi = min(x < 0 ? NONE : lab_min(c, x), edge_min(c, r));
                     uint32_t h = uf_prio(rep, 0) & (RS - 1);
                     while (true) {  // kept below RS / 2 keys before every batch of TB
                         const int32_t k = atomicCAS(&skey[h], -1, rep);
@@ -660,8 +688,8 @@ __global__ __launch_bounds__(TB) void dc_mid(DC c, int J, int LM, int LB, int *_
                         const int32_t rep = c.hooked[r];
                         const LRec q = c.lr[rep];
                         if (q.rootedge == (int32_t)r) {
-                            c.esize[r] = q.csize + (rep < c.n ? 1 : c.esize[rep - c.n]);
-                            c.eminid[r] = min(q.cmin, rep < c.n ? vid(c, rep) : c.eminid[rep - c.n]);
+                            c.esize[r] = q.csize + lab_size(c, rep);
+                            c.eminid[r] = min(q.cmin, lab_min(c, rep));
                         }
                     }
                     const int64_t u = r | half;
@@ -753,8 +781,8 @@ __global__ __launch_bounds__(TB) void dc_block(DC c, int *__restrict__ err) {
             while (true) {  // <= 2B keys in 4B slots
                 const int32_t old = atomicCAS(&key[h], -1, x);
                 if (old == -1) {
-                    bsz[h] = x < c.n ? 1 : c.esize[x - c.n];
-                    bmn[h] = x < c.n ? vid(c, x) : c.eminid[x - c.n];
+                    bsz[h] = lab_size(c, x);
+                    bmn[h] = lab_min(c, x);
                     break;
                 }
                 if (old == x) break;
@@ -813,6 +841,10 @@ __global__ __launch_bounds__(TB) void dc_block(DC c, int *__restrict__ err) {
                 if (x >= 0) {  // a hooked label is never a representative: its cs / cm are its base
                     atomicAdd(&cs[rep], cs[x]);
                     atomicMin(&cm[rep], cm[x]);
+                }
+                if (c.wl) {
+                    atomicAdd(&cs[rep], c.wl[lo + k]);
+                    atomicMin(&cm[rep], c.ml[lo + k]);
                 }
             }
             __syncthreads();
@@ -873,8 +905,8 @@ __global__ __launch_bounds__(64) void dc_local(DC c, int *__restrict__ err) {
                 if (old == -1) {  // inserted: initialise the slot
                     luf[h] = (int16_t)h;
                     lre[h] = -1;
-                    lsz[h] = x < c.n ? 1 : c.esize[x - c.n];
-                    lmn[h] = x < c.n ? vid(c, x) : c.eminid[x - c.n];
+                    lsz[h] = lab_size(c, x);
+                    lmn[h] = lab_min(c, x);
                     break;
                 }
                 if (old == x) break;
@@ -906,8 +938,8 @@ __global__ __launch_bounds__(64) void dc_local(DC c, int *__restrict__ err) {
                     b = t;
                 }
                 luf[b] = (int16_t)a;
-                lsz[a] += lsz[b];
-                lmn[a] = min(lmn[a], lmn[b]);
+                lsz[a] += lsz[b] + edge_size(c, lo + k);
+                lmn[a] = min(min(lmn[a], lmn[b]), edge_min(c, lo + k));
                 lre[a] = (int16_t)k;
                 c.esize[lo + k] = lsz[a];
                 c.eminid[lo + k] = lmn[a];
@@ -915,6 +947,222 @@ __global__ __launch_bounds__(64) void dc_local(DC c, int *__restrict__ err) {
         }
         __syncthreads();
     }
+}
+
+// ------------------------------------------------ 2b. Kruskal tree by alpha-edge contraction
+// Call an edge alpha when it is the lightest edge of neither endpoint (m(p) = pparent[p]).  A
+// non-alpha edge joins a single point (two, for the one edge per group that is m() of both
+// ends) to a component, so it never branches the dendrogram: only alpha edges do, and fewer
+// than half the edges are alpha (the non-alpha ones are the n values of m() minus the groups,
+// at most n / 2 of them).  The non-alpha edges form a forest whose trees, the super-vertices,
+// the alpha edges connect into a tree of their own; that tree's dendrogram is the full one
+// restricted to alpha edges, because the path inside a super-vertex between two alpha
+// attachments is lighter than the heavier of the two.  So the divide and conquer above runs on
+// the alpha tree alone, and the other edges fall on chains: sorted by (the component they
+// extend, rank), a segmented scan gives every one its size, smallest id and parent.
+//
+// The forest needs no union: a non-alpha edge with one m() end points to m() of its other end
+// (a lighter non-alpha edge of the same group), the edge with two is the root.  Whatever the
+// input, these pointers descend in rank, so a cycle of the input always closes through an alpha
+// edge and shows in the alpha tree's dc_unite.
+struct __align__(8) CMin {
+    int32_t s, mn;  // points added, smallest of them
+};
+struct CMinOp {
+    __host__ __device__ CMin operator()(const CMin &a, const CMin &b) const {
+        return CMin{a.s + b.s, a.mn < b.mn ? a.mn : b.mn};
+    }
+};
+
+struct KA {
+    const int32_t *ea, *eb, *pparent;
+    int32_t *up;        // m: forest of the non-alpha edges
+    uint64_t *f2, *p2;  // m: flags and their exclusive sums: alpha in the low word, roots in the high
+    CMin *cv;           // m: (c(e), cmin(e))
+    int32_t *ev;        // m: super-vertex of a non-alpha edge
+    int32_t *proot, *ppos;  // n: roots by smallest end point, for point-order vertex labels (nullable)
+    int32_t *a0;        // super-vertex -> its smallest alpha index
+    int32_t *arank;     // alpha index -> rank
+    int32_t *lab0;      // the alpha tree's endpoint labels, kept for the second pass
+    int32_t *anc;       // lifting rows over the alpha parents, stride ma + 1, index ma = none
+    int32_t *wv, *mv, *wl, *ml, *lfirst;  // run totals; first edge of the chain above an alpha edge
+    int32_t *exm;       // smallest id of C(a) without a's own chain
+    uint32_t *kin, *kout;
+    int32_t *vin, *vout;
+    CMin *sin, *sout;
+    int64_t *cnt;  // alpha edges, super-vertices
+    int64_t m, cap;  // cap: alpha indices the arrays hold
+};
+
+__global__ void ka_classify(KA k) {
+    HDB_GRID_STRIDE(e, k.m) {
+        const int32_t u = k.ea[e], v = k.eb[e], mu = k.pparent[u], mv = k.pparent[v];
+        const int cu = mu == (int32_t)e, cv = mv == (int32_t)e, c = cu + cv;
+        k.f2[e] = (uint64_t)(c == 0) | ((uint64_t)(c == 2) << 32);
+        k.up[e] = c == 1 ? (cu ? mv : mu) : (int32_t)e;  // the other end's m() is lighter than e
+        k.cv[e] = CMin{c, min(cu ? u : NONE, cv ? v : NONE)};
+        if (c == 2 && k.proot) k.proot[min(u, v)] = 1;
+    }
+}
+
+__global__ void ka_find(KA k) {
+    HDB_GRID_STRIDE(e, k.m) {
+        if (e == k.m - 1) {
+            const uint64_t t = k.p2[e] + k.f2[e];
+            k.cnt[0] = (int64_t)(t & 0xffffffffu);
+            k.cnt[1] = (int64_t)(t >> 32);
+        }
+        if (k.f2[e] & 1) continue;
+        const int32_t r = up_find(k.up, (int32_t)e);
+        k.ev[e] = k.ppos ? k.ppos[min(k.ea[r], k.eb[r])] : (int32_t)(k.p2[r] >> 32);
+    }
+}
+
+__global__ void ka_alpha(KA k, DC c) {
+    HDB_GRID_STRIDE(e, k.m) {
+        if (!(k.f2[e] & 1)) continue;
+        const int64_t a = (int64_t)(k.p2[e] & 0xffffffffu);
+        if (a >= k.cap) continue;  // not a tree: the host sees the count
+        k.arank[a] = (int32_t)e;
+        c.parent[a] = NONE;
+#pragma unroll
+        for (int s = 0; s < 2; s++) {
+            const int32_t V = k.ev[k.pparent[s ? k.eb[e] : k.ea[e]]];
+            c.lab[2 * a + s] = V;
+            k.lab0[2 * a + s] = V;
+            atomicMin(&k.a0[V], (int32_t)a);
+        }
+    }
+}
+
+// everything indexed by alpha index or super-vertex that the passes expect initialised
+__global__ void ka_init(KA k, DC c) {
+    HDB_GRID_STRIDE(i, 2 * k.cap + 1) {
+        c.stamp[i] = -1;
+        if (i <= k.cap) k.a0[i] = NONE;
+        if (i < k.cap) {
+            k.wl[i] = 0;
+            k.ml[i] = NONE;
+            k.lfirst[i] = NONE;
+        }
+    }
+}
+
+// row 0 of the lifting table: the first pass's parents
+__global__ void ka_anc0(KA k, DC c) {
+    HDB_GRID_STRIDE(a, c.m + 1) {
+        const int32_t p = a < c.m ? c.parent[a] : NONE;
+        k.anc[a] = p == NONE ? (int32_t)c.m : p;
+    }
+}
+
+// Sort key of an edge: super-vertex V for V's bottom chain (the edges below V's first alpha
+// edge: C(e) lies inside V), na + b for the chain above alpha edge b, the heaviest alpha edge
+// in C(e) -- the last ancestor-or-self of a0(V) with index < apos(e); indices rise along the
+// way up, so the lifting rows find it in `rows` steps.  Alpha edges sort last.
+__global__ void ka_keys(KA k, int64_t ma, int64_t na, int rows) {
+    HDB_GRID_STRIDE(e, k.m) {
+        uint32_t key = (uint32_t)(2 * ma + 1);
+        if (!(k.f2[e] & 1)) {
+            const int32_t V = k.ev[e], a0v = k.a0[V], ap = (int32_t)(k.p2[e] & 0xffffffffu);
+            key = (uint32_t)V;
+            if (a0v != NONE && ap > a0v) {
+                int32_t b = a0v;
+                for (int j = rows - 1; j >= 0; j--) {
+                    const int32_t t = k.anc[(int64_t)j * (ma + 1) + b];
+                    if (t < ap) b = t;  // none = ma >= ap
+                }
+                key = (uint32_t)(na + b);
+            }
+        }
+        k.kin[e] = key;
+        k.vin[e] = (int32_t)e;
+    }
+}
+
+__global__ void ka_gather(KA k) {
+    HDB_GRID_STRIDE(i, k.m) k.sin[i] = k.cv[k.vout[i]];
+}
+
+// run totals and, for the chain above an alpha edge, its first edge
+__global__ void ka_runs(KA k, int64_t ma, int64_t na) {
+    const int64_t cnt = k.m - ma;  // the non-alpha edges come first
+    HDB_GRID_STRIDE(i, cnt) {
+        const uint32_t key = k.kout[i];
+        if (i == 0 || k.kout[i - 1] != key)
+            if (key >= na) k.lfirst[key - na] = k.vout[i];
+        if (i == cnt - 1 || k.kout[i + 1] != key) {
+            const CMin t = k.sout[i];
+            if (key < na) {
+                k.wv[key] = t.s;
+                k.mv[key] = t.mn;
+            } else {
+                k.wl[key - na] = t.s;
+                k.ml[key - na] = t.mn;
+            }
+        }
+    }
+}
+
+__global__ void ka_reset(KA k, DC c) {
+    HDB_GRID_STRIDE(i, c.n + c.m) {
+        c.stamp[i] = -1;
+        if (i < c.m) {
+            c.parent[i] = NONE;
+            k.exm[i] = NONE;
+            c.lab[2 * i] = k.lab0[2 * i];
+            c.lab[2 * i + 1] = k.lab0[2 * i + 1];
+        }
+    }
+}
+
+// The second pass's eminid includes the chain above the edge itself; C(a) alone is its two
+// sides: an alpha child with its chain, or a super-vertex whose first alpha edge a is.
+__global__ void ka_exmin(KA k, DC c) {
+    HDB_GRID_STRIDE(i, c.n + c.m) {
+        if (i < c.m) {
+            const int32_t p = k.anc[i];
+            if (p != (int32_t)c.m) atomicMin(&k.exm[p], c.eminid[i]);
+        } else {
+            const int32_t a = k.a0[i - c.m];
+            if (a != NONE) atomicMin(&k.exm[a], k.mv[i - c.m]);
+        }
+    }
+}
+
+// the arrays in rank space, one thread per sorted position (the alpha edges last, in rank order)
+__global__ void ka_write(KA k, DC c, int32_t *__restrict__ parent, int32_t *__restrict__ esize,
+                         int32_t *__restrict__ eminid, int *__restrict__ err) {
+    const int64_t ma = c.m, na = c.n, cnt = k.m - ma;
+    int bad = 0;
+    auto rank_of = [&](int32_t a) { return a == NONE || a == (int32_t)ma ? NONE : k.arank[a]; };
+    HDB_GRID_STRIDE(i, k.m) {
+        const int32_t e = k.vout[i];
+        if (i >= cnt) {
+            const int64_t a = i - cnt;
+            esize[e] = c.esize[a] - k.wl[a];
+            eminid[e] = k.exm[a];
+            const int32_t pa = k.anc[a], f = k.lfirst[a];
+            parent[e] = f != NONE ? f : rank_of(pa);
+            if (c.parent[a] != (pa == (int32_t)ma ? NONE : pa)) bad = FE_PASS;  // the passes must agree
+            continue;
+        }
+        const uint32_t key = k.kout[i];
+        const CMin t = k.sout[i];
+        int32_t base = 0, bmin = NONE, last;
+        if (key < na) {
+            last = rank_of(k.a0[key]);
+        } else {
+            const int64_t b = key - na;
+            base = c.esize[b] - k.wl[b];
+            bmin = k.exm[b];
+            last = rank_of(k.anc[b]);
+        }
+        esize[e] = base + t.s;
+        eminid[e] = min(bmin, t.mn);
+        parent[e] = i + 1 < cnt && k.kout[i + 1] == key ? k.vout[i + 1] : last;
+    }
+    flag_or(err, bad);
 }
 
 // -------------------------------------------------------------------- 3. nodes + clusters
@@ -2048,6 +2296,7 @@ void throw_tree_errors(int e) {
     if (e & FE_CYCLE) HDB_THROW(HDB_EINVAL, "flat labels: the edges contain a cycle");
     if (e & FE_ROOTS) HDB_THROW(HDB_EINVAL, "flat labels: the edges are not a spanning tree");
     if (e & FE_JUMP) HDB_THROW(HDB_EDEVICE, "flat labels: pointer jumping did not converge in its launch budget");
+    if (e & FE_PASS) HDB_THROW(HDB_EDEVICE, "flat labels: the two passes over the contracted tree disagree");
 }
 
 }  // namespace
@@ -2082,11 +2331,19 @@ static void flat_device_impl(hdb_ctx *ctx, const int32_t *va, const int32_t *vb,
     double *cw, *ew;
     int64_t *words;
     DC dc;
+    // 2b: trees of FLAT_CONTRACT_MIN_M edges or more build the Kruskal tree by contraction; fewer
+    // than m / 2 edges are alpha, so acap alpha indices and arows lifting rows hold any tree's
+    const bool contract = m >= FLAT_CONTRACT_MIN_M;
+    const int64_t acap = m / 2 + 1;
+    int arows = 1;
+    while ((int64_t(1) << arows) < acap) arows++;
+    DC da{};
+    KA ka{};
     carve(ctx, A_FLAT0, [&](Carver &cv) {
         keep = cv.take<int32_t>(ne), pos = cv.take<int32_t>(ne);
         ca = cv.take<int32_t>(mm), cb = cv.take<int32_t>(mm);
         cw = cv.take<double>(mm);
-        words = cv.take<int64_t>(4);  // m_dev, err, flags, the cluster count
+        words = cv.take<int64_t>(6);  // m_dev, err, flags, the cluster count, 2b's two counts
         ea = cv.take<int32_t>(mm), eb = cv.take<int32_t>(mm);
         ew = cv.take<double>(mm);
         dc.lab = cv.take<int32_t>(2 * mm);
@@ -2098,6 +2355,24 @@ static void flat_device_impl(hdb_ctx *ctx, const int32_t *va, const int32_t *vb,
         dc.esize = cv.take<int32_t>(mm);
         dc.eminid = cv.take<int32_t>(mm);
         pparent = cv.take<int32_t>(n);
+        if (!contract) return;
+        // 2b: the alpha tree's own divide-and-conquer arrays (acap edges, acap + 1 vertices)
+        da.lab = cv.take<int32_t>(2 * acap), ka.lab0 = cv.take<int32_t>(2 * acap);
+        da.lr = cv.take<LRec>(2 * acap + 1);
+        da.stamp = cv.take<int32_t>(2 * acap + 1);
+        da.hooked = cv.take<int32_t>(acap), da.parent = cv.take<int32_t>(acap);
+        da.esize = cv.take<int32_t>(acap), da.eminid = cv.take<int32_t>(acap);
+        ka.a0 = cv.take<int32_t>(acap + 1), ka.arank = cv.take<int32_t>(acap);
+        ka.wv = cv.take<int32_t>(acap + 1), ka.mv = cv.take<int32_t>(acap + 1);
+        ka.wl = cv.take<int32_t>(acap), ka.ml = cv.take<int32_t>(acap), ka.lfirst = cv.take<int32_t>(acap);
+        ka.exm = cv.take<int32_t>(acap);
+        ka.anc = cv.take<int32_t>((acap + 1) * arows);
+        ka.up = cv.take<int32_t>(mm), ka.ev = cv.take<int32_t>(mm);
+        ka.f2 = cv.take<uint64_t>(mm), ka.p2 = cv.take<uint64_t>(mm);
+        ka.cv = cv.take<CMin>(mm), ka.sin = cv.take<CMin>(mm), ka.sout = cv.take<CMin>(mm);
+        ka.kin = cv.take<uint32_t>(mm), ka.kout = cv.take<uint32_t>(mm);
+        ka.vin = cv.take<int32_t>(mm), ka.vout = cv.take<int32_t>(mm);
+        ka.proot = cv.take<int32_t>(n), ka.ppos = cv.take<int32_t>(n);
     });
     int64_t *m_dev = words;
     int *err = (int *)(words + 1), *flags = (int *)(words + 2);
@@ -2153,57 +2428,116 @@ static void flat_device_impl(hdb_ctx *ctx, const int32_t *va, const int32_t *vb,
         perm = i2;
     }
     hipLaunchKernelGGL(fl_rank, dim3(g), dim3(256), 0, st, ca, cb, cw, m, desc, perm, ea, eb, ew, dc.lab, dc.parent);
-    hipLaunchKernelGGL(fill_i32, dim3(grid_for(nv + m)), dim3(256), 0, st, dc.stamp, nv + m, -1);
+    if (!contract) hipLaunchKernelGGL(fill_i32, dim3(grid_for(nv + m)), dim3(256), 0, st, dc.stamp, nv + m, -1);
     hipLaunchKernelGGL(fill_i32, dim3(grid_for(n)), dim3(256), 0, st, pparent, n, NONE);
     hipLaunchKernelGGL(fl_point_parent, dim3(g), dim3(256), 0, st, ea, eb, m, pparent);
-    if (relabel) {
+    if (relabel && !contract) {  // (2b numbers its super-vertices in rank order itself)
         hipLaunchKernelGGL(fl_relabel_orig, dim3(grid_for(n)), dim3(256), 0, st, pparent, eb, n, orig);
         hipLaunchKernelGGL(fl_relabel, dim3(g), dim3(256), 0, st, ea, eb, pparent, m, dc.lab);
     }
 
-    // ---- 2. Kruskal tree by rank divide and conquer
-    int J = 0;
-    while ((int64_t(1) << J) <= m) J++;  // 2^J > m: every rank < m has a clear bit below J
-    // global depths split blocks down to 2^LB ranks; dc_block (dc_local) finishes each such block
-    const int LB = ctx->flat_block_log >= 8 && ctx->flat_block_log <= 10 ? ctx->flat_block_log : LOC_LOG;
-    // depths LM-1 .. LB per workgroup (dc_mid), the shallower ones global
-    const int LM = ctx->flat_mid_log > LB ? std::max(LB, std::min(ctx->flat_mid_log, J)) : LB;
-    ctx->stats["flat_global_depths"] = std::max(0, J - LM);  // what this call runs (tests of the variants)
-    ctx->stats["flat_mid_depths"] = LM - LB;
-    for (int j = 0; j < J - LM; j++) {
-        const int b = J - 1 - j;
-        // L ranks (bit b clear) below m; every U rank is an L rank + 2^b
-        const int64_t blk = int64_t(1) << (b + 1), half = int64_t(1) << b;
-        const int64_t nl = (m / blk) * half + std::min(m % blk, half);
-        const int gl = grid_for(nl);
-        hipLaunchKernelGGL(dc_init, dim3(gl), dim3(256), 0, st, dc, b, j, nl);
-        hipLaunchKernelGGL(dc_unite, dim3(gl), dim3(256), 0, st, dc, b, nl, err);
-        // deep depths: small components, no hot records -- the per-workgroup LDS tables only
-        // cost occupancy (the multi-batch kernels run nl / 4096 workgroups)
-        const bool deep = j >= ctx->flat_deep_depth;
-        switch (deep ? ctx->flat_deep_root : ctx->flat_root_variant) {
-        case 1: hipLaunchKernelGGL((dc_root<1024, 4096>), dim3((unsigned)ceil_div(nl, 1024)), dim3(1024), 0, st, dc, b, j, nl); break;
-        case 2: hipLaunchKernelGGL(dc_root_direct, dim3(gl), dim3(256), 0, st, dc, b, j, nl); break;
-        case 3: hipLaunchKernelGGL((dc_root_multi<1024, 4096, 4>), dim3((unsigned)ceil_div(nl, 4096)), dim3(1024), 0, st, dc, b, j, nl); break;
-        case 4: hipLaunchKernelGGL((dc_root_multi<1024, 8192, 4>), dim3((unsigned)ceil_div(nl, 4096)), dim3(1024), 0, st, dc, b, j, nl); break;
-        case 5: hipLaunchKernelGGL((dc_root_multi<512, 4096, 4>), dim3((unsigned)ceil_div(nl, 2048)), dim3(512), 0, st, dc, b, j, nl); break;
-        default: hipLaunchKernelGGL((dc_root<ROOT_TB, ROOT_SLOTS>), dim3(gl), dim3(ROOT_TB), 0, st, dc, b, j, nl);
+    // ---- 2. Kruskal tree by rank divide and conquer: of all edges, or (2b) of the alpha edges
+    auto kruskal_dc = [&](const DC &c) {
+        const int64_t m = c.m;
+        int J = 0;
+        while ((int64_t(1) << J) <= m) J++;  // 2^J > m: every rank < m has a clear bit below J
+        // global depths split blocks down to 2^LB ranks; dc_block (dc_local) finishes each such block
+        const int LB = ctx->flat_block_log >= 8 && ctx->flat_block_log <= 10 ? ctx->flat_block_log : LOC_LOG;
+        // depths LM-1 .. LB per workgroup (dc_mid), the shallower ones global
+        const int LM = ctx->flat_mid_log > LB ? std::max(LB, std::min(ctx->flat_mid_log, J)) : LB;
+        ctx->stats["flat_global_depths"] = std::max(0, J - LM);  // what this call runs (tests of the variants)
+        ctx->stats["flat_mid_depths"] = LM - LB;
+        if (m == 0) return;
+        for (int j = 0; j < J - LM; j++) {
+            const int b = J - 1 - j;
+            // L ranks (bit b clear) below m; every U rank is an L rank + 2^b
+            const int64_t blk = int64_t(1) << (b + 1), half = int64_t(1) << b;
+            const int64_t nl = (m / blk) * half + std::min(m % blk, half);
+            const int gl = grid_for(nl);
+            hipLaunchKernelGGL(dc_init, dim3(gl), dim3(256), 0, st, c, b, j, nl);
+            hipLaunchKernelGGL(dc_unite, dim3(gl), dim3(256), 0, st, c, b, nl, err);
+            // deep depths: small components, no hot records -- the per-workgroup LDS tables only
+            // cost occupancy (the multi-batch kernels run nl / 4096 workgroups)
+            const bool deep = j >= ctx->flat_deep_depth;
+            switch (deep ? ctx->flat_deep_root : ctx->flat_root_variant) {
+            case 1: hipLaunchKernelGGL((dc_root<1024, 4096>), dim3((unsigned)ceil_div(nl, 1024)), dim3(1024), 0, st, c, b, j, nl); break;
+            case 2: hipLaunchKernelGGL(dc_root_direct, dim3(gl), dim3(256), 0, st, c, b, j, nl); break;
+            case 3: hipLaunchKernelGGL((dc_root_multi<1024, 4096, 4>), dim3((unsigned)ceil_div(nl, 4096)), dim3(1024), 0, st, c, b, j, nl); break;
+            case 4: hipLaunchKernelGGL((dc_root_multi<1024, 8192, 4>), dim3((unsigned)ceil_div(nl, 4096)), dim3(1024), 0, st, c, b, j, nl); break;
+            case 5: hipLaunchKernelGGL((dc_root_multi<512, 4096, 4>), dim3((unsigned)ceil_div(nl, 2048)), dim3(512), 0, st, c, b, j, nl); break;
+            default: hipLaunchKernelGGL((dc_root<ROOT_TB, ROOT_SLOTS>), dim3(gl), dim3(ROOT_TB), 0, st, c, b, j, nl);
+            }
+            if ((deep ? ctx->flat_deep_link : ctx->flat_link_variant) == 1)
+                hipLaunchKernelGGL((dc_link_multi<1024, 8192, 2>), dim3((unsigned)ceil_div(nl, 2048)), dim3(1024), 0, st,
+                                   c, b, j, nl);
+            else
+                hipLaunchKernelGGL(dc_link, dim3(gl), dim3(256), 0, st, c, b, j, nl);
         }
-        if ((deep ? ctx->flat_deep_link : ctx->flat_link_variant) == 1)
-            hipLaunchKernelGGL((dc_link_multi<1024, 8192, 2>), dim3((unsigned)ceil_div(nl, 2048)), dim3(1024), 0, st, dc,
-                               b, j, nl);
-        else
-            hipLaunchKernelGGL(dc_link, dim3(gl), dim3(256), 0, st, dc, b, j, nl);
-    }
-    if (LM > LB)
-        hipLaunchKernelGGL(dc_mid<1024>, dim3((unsigned)ceil_div(m, int64_t(1) << LM)), dim3(1024), 0, st, dc, J, LM, LB,
-                           err);
-    const unsigned nblk = (unsigned)std::min<int64_t>(ceil_div(m, int64_t(1) << LB), 65536);
-    switch (ctx->flat_block_log) {
-    case 8: hipLaunchKernelGGL((dc_block<8, 128>), dim3(nblk), dim3(128), 0, st, dc, err); break;
-    case 9: hipLaunchKernelGGL((dc_block<9, 256>), dim3(nblk), dim3(256), 0, st, dc, err); break;
-    case 10: hipLaunchKernelGGL((dc_block<10, 512>), dim3(nblk), dim3(512), 0, st, dc, err); break;
-    default: hipLaunchKernelGGL(dc_local, dim3(nblk), dim3(64), 0, st, dc, err);
+        if (LM > LB)
+            hipLaunchKernelGGL(dc_mid<1024>, dim3((unsigned)ceil_div(m, int64_t(1) << LM)), dim3(1024), 0, st, c, J, LM,
+                               LB, err);
+        const unsigned nblk = (unsigned)std::min<int64_t>(ceil_div(m, int64_t(1) << LB), 65536);
+        switch (ctx->flat_block_log) {
+        case 8: hipLaunchKernelGGL((dc_block<8, 128>), dim3(nblk), dim3(128), 0, st, c, err); break;
+        case 9: hipLaunchKernelGGL((dc_block<9, 256>), dim3(nblk), dim3(256), 0, st, c, err); break;
+        case 10: hipLaunchKernelGGL((dc_block<10, 512>), dim3(nblk), dim3(512), 0, st, c, err); break;
+        default: hipLaunchKernelGGL(dc_local, dim3(nblk), dim3(64), 0, st, c, err);
+        }
+    };
+    ctx->stats["flat_contract"] = contract ? 1 : 0;
+    ctx->stats["flat_alpha_edges"] = 0;
+    if (!contract) {
+        kruskal_dc(dc);
+    } else {
+        // ---- 2b. the alpha tree twice (parents, then sizes over the chains' totals), the chains
+        // by one stable sort and one segmented scan.  One read-back sizes the alpha tree's depths.
+        ka.ea = ea, ka.eb = eb, ka.pparent = pparent;
+        ka.cnt = words + 4;
+        ka.m = m, ka.cap = acap;
+        if (!relabel) {  // point-order vertex labels: super-vertices numbered by their root's smaller end
+            HIP_CHECK(hipMemsetAsync(ka.proot, 0, sizeof(int32_t) * n, st));
+        } else {
+            ka.proot = ka.ppos = nullptr;
+        }
+        hipLaunchKernelGGL(ka_init, dim3(grid_for(2 * acap + 1)), dim3(256), 0, st, ka, da);
+        hipLaunchKernelGGL(ka_classify, dim3(g), dim3(256), 0, st, ka);
+        exclusive_sum(ctx, A_FLAT_TMP, ka.f2, ka.p2, m);
+        if (!relabel) exclusive_sum(ctx, A_FLAT_TMP, ka.proot, ka.ppos, n);
+        hipLaunchKernelGGL(ka_find, dim3(g), dim3(256), 0, st, ka);
+        hipLaunchKernelGGL(ka_alpha, dim3(g), dim3(256), 0, st, ka, da);
+        HIP_CHECK(hipMemcpyAsync(pin, ka.cnt, sizeof(int64_t) * 2, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        const int64_t ma = pin[0], na = pin[1];
+        // every point is an end of its m(): n - na non-alpha edges, unless a point has no edge
+        if (ma != na - 1 || ma >= acap) HDB_THROW(HDB_EINVAL, "flat labels: the edges contain a cycle");
+        ctx->stats["flat_alpha_edges"] = ma;
+        da.n = na;
+        da.m = ma;
+        kruskal_dc(da);
+        int rows = 0;
+        while ((int64_t(1) << rows) < ma) rows++;  // 2^rows - 1 >= the longest climb, ma - 1 hops
+        const int ga = grid_for(ma + 1);
+        hipLaunchKernelGGL(ka_anc0, dim3(ga), dim3(256), 0, st, ka, da);
+        for (int j = 1; j < rows; j++)
+            hipLaunchKernelGGL(lc_double, dim3(ga), dim3(256), 0, st, ka.anc + (j - 1) * (ma + 1), ka.anc + j * (ma + 1),
+                               (int32_t)ma);
+        hipLaunchKernelGGL(ka_keys, dim3(g), dim3(256), 0, st, ka, ma, na, rows);
+        int bits = 1;
+        while ((int64_t(1) << bits) < 2 * ma + 2) bits++;
+        sort_pairs(ctx, A_FLAT_TMP, ka.kin, ka.kout, ka.vin, ka.vout, m, 0, bits);
+        hipLaunchKernelGGL(ka_gather, dim3(g), dim3(256), 0, st, ka);
+        with_tmp(ctx, A_FLAT_TMP, [&](void *tmp, size_t &b) {
+            return rocprim::inclusive_scan_by_key(tmp, b, ka.kout, ka.sin, ka.sout, (size_t)m, CMinOp(),
+                                                  rocprim::equal_to<uint32_t>(), st);
+        });
+        hipLaunchKernelGGL(ka_runs, dim3(g), dim3(256), 0, st, ka, ma, na);
+        if (ma > 0) {
+            hipLaunchKernelGGL(ka_reset, dim3(grid_for(na + ma)), dim3(256), 0, st, ka, da);
+            da.wv = ka.wv, da.mv = ka.mv, da.wl = ka.wl, da.ml = ka.ml;
+            kruskal_dc(da);
+            hipLaunchKernelGGL(ka_exmin, dim3(grid_for(na + ma)), dim3(256), 0, st, ka, da);
+        }
+        hipLaunchKernelGGL(ka_write, dim3(g), dim3(256), 0, st, ka, da, dc.parent, dc.esize, dc.eminid, err);
     }
 
     // ---- 3. multi-way nodes, condensation

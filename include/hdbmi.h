@@ -138,7 +138,9 @@ int hdb_ctx_synchronize(hdb_ctx *ctx);
  *                                  (0..1, default 1): the kernels of the global depths (A/B);
  *                                  "flat_deep_depth" (default 64): global depths >= it use
  *                                  "flat_deep_root" / "flat_deep_link" instead; stats
- *                                  "flat_global_depths" / "flat_mid_depths" of the last call;
+ *                                  "flat_global_depths" / "flat_mid_depths" of the last call
+ *                                  (of its contracted tree when "flat_contract" is 1: trees of
+ *                                  2^18 edges or more, "flat_alpha_edges" edges of which branch);
  *   "prim_coop_bs"    (default 1024; 0, 128..1024): cooperative Prim workgroup size, 0 = the
  *                                  smallest that keeps the Prim within 32 workgroups; stats
  *                                  "prim_coop_last_bs" / "prim_coop_last_spread" of the last one;
